@@ -11,12 +11,15 @@ from torch.manual_seed(0) if absent).
 A "step" is one lock-step MCTS iteration of every tree on the rank: expand the leaf's 12 children (HIP), policy /
 value network on the NEW children (11 packed rows per tree; PyTorch-ROCm GEMMs), backup + PUCT descent (HIP).
 
-What is timed.  The 1 024 tree slots are fed from a pool of `--pool-factor` x 1 024 scrambles: a finished tree
+What is timed.  The 1 024 tree slots are fed from a pool of `--pool-factor` x 1 024 scrambles (by default 8, more when K
+needs more: POOL_STEPS_PER_FACTOR): a finished tree
 hands its slot to the next waiting scramble (continuous batching), so the slots hold trees of every age.  The
 pool is first advanced UNTIMED until as many scrambles again as there are slots have been started (the age mix
 is then that of a long-running evaluation), then W warm-up steps, then EXACTLY K steps are timed between
 barrier + synchronize on both sides, harvesting and refilling included:
-  value = unique states inserted into the trees of all ranks during the K timed steps / max-over-ranks seconds.
+  value = unique states inserted into the trees of all ranks during the K timed steps / max-over-ranks seconds,
+  ms_per_step = those seconds / K.  A pool that runs dry before K steps (a --pool-factor too small) ends the run with an error.
+`--dump-outputs DIR` writes what the timed steps computed, as of the last one, to DIR/<leg>_<name>.npy (outside the timing).
 This is done once per network precision (a "leg"):
   f32s  fp32 accuracy on the f16 matrix cores (the reference's net runs in fp32, librubiks/model.py:131-141)  ->  `value`, `dtype`
   f32   the fp32 MFMA GEMM chain as is (window only)          bf16  the fast engine  ->  `legs.*`
@@ -157,6 +160,22 @@ def cpu_adi(model, games=64, depth=32):
                       f"NumPy cube ops + torch CPU fp32 value network, {dt:.1f} s"}
 
 
+# Default pool size: the slots must still be fed when the last of the --steps timed steps runs.  A slot takes on a new scramble
+# about every 1 200 steps or more (8 x 1 024 scrambles on 1 024 slots: 1 000 steps of prep, then 10 700 steps to the end of the
+# pool in bf16, 14 100 at fp32 accuracy), so every POOL_STEPS_PER_FACTOR steps of warm-up and window get one more scramble per
+# slot, on top of the two of the prep and one in reserve.  Up to 5 000 steps that is the pool of 8 x slots as it always was.
+POOL_STEPS_PER_FACTOR = 1000
+
+
+def write_outputs(out_dir, leg, arrays, rank, world):
+    """--dump-outputs: DIR/<leg>_<name>.npy (DIR/rank<r>_<leg>_<name>.npy when there is more than one rank)."""
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_{leg}" if world > 1 else leg
+    for key, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (key, arr.dtype)
+        np.save(os.path.join(out_dir, f"{prefix}_{key}.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -184,7 +203,8 @@ def main():
     ap.add_argument("--config5-max-states", type=int, default=175000,
                     help="per-tree cap of the config5 leg = the reference's max_states: 8 192 x 175 001 node rows (408 GB) are reserved address "
                          "space, memory is mapped behind the rows the trees reach (rounds 1-3 allocated up front and had to stop at 50 000)")
-    ap.add_argument("--pool-factor", type=int, default=8, help="scrambles in the pool per tree slot")
+    ap.add_argument("--pool-factor", type=int, default=None,
+                    help="scrambles in the pool per tree slot (default: 8, more when --steps needs more, see POOL_STEPS_PER_FACTOR)")
     ap.add_argument("--prep-cap", type=int, default=4000, help="most untimed iterations before the timed window")
     ap.add_argument("--window-only", action="store_true", help="skip the pool's tail and the runs to completion")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -207,11 +227,17 @@ def main():
     ap.add_argument("--as-rank", default=None, metavar="R/W",
                     help="single process, no process group: take rank R's share of a W-rank run's scrambles (tests compare "
                          "the ranks of a distributed run with these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed steps computed, as of the last one, to DIR/<leg>_<name>.npy (float32 / float64, a few MB): "
+                         "per-tree state, the first node rows of every tree, the network outputs of the last step (tools/benchlib/legs.py "
+                         "window_outputs).  The inputs are seeded, so two builds run with the same arguments can be compared array for array")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="file that receives the full result (per-leg detail, phases, the roofline_env ladder); the stdout line names it")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and not args.as_rank:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))   # no launcher around us: start the ranks ourselves (before any HIP call)
+    if args.pool_factor is None:
+        args.pool_factor = max(8, 3 + -(-(args.warmup + args.steps) // POOL_STEPS_PER_FACTOR))
     if args.level_budget != "auto":
         args.level_budget = int(args.level_budget)
     legs = [x.split(":")[0] for x in args.legs.split(",") if x]
@@ -265,8 +291,13 @@ def main():
 
     results, extras = {}, {}
     for name in legs:
+        dump = {} if args.dump_outputs else None
         leg, engine, agent = run_leg(name, model, pool_roots, config_roots, args, world, coll_device, args.trees, args.solve_max_states,
-                                     window_only=args.window_only or leg_window_only[name], full_warm=False)
+                                     window_only=args.window_only or leg_window_only[name], full_warm=False, dump=dump)
+        if leg["steps_timed"] != args.steps:     # ms_per_step is the time of one of exactly --steps steps, or there is no result
+            sys.exit(f"bench: the '{name}' pool ran dry after {leg['steps_timed']} of the {args.steps} timed steps; raise --pool-factor")
+        if dump:
+            write_outputs(args.dump_outputs, name, dump, rank, world)
         results[name] = leg
         if rank == 0:
             progress(f"mcts leg {name} done")

@@ -37,8 +37,9 @@ def golden_cases(npz, prefix):
     return sorted(k[len(prefix):-len("_params")] for k in npz.files if k.startswith(prefix) and k.endswith("_params"))
 
 
-@pytest.fixture(scope="session")
+@pytest.fixture(scope="module")
 def standin_net(agents_golden):
+    """A fresh CPU copy per test module: GPU tests move theirs to the device (`.cuda()` moves a module in place)."""
     from standin_net import StandInNet
     return StandInNet(weights={k[4:]: agents_golden[k] for k in agents_golden.files
                                if k.startswith("net_") and not k.startswith("net_probe")})

@@ -46,11 +46,38 @@ def _entry(target, rank, args, q, err_path):
             os._exit(1)
 
 
-def run_ranks(target, world: int, make_args, timeout: float = 300.0) -> list:
+# The environment of ranks that stay on the CPU: no device is visible, and torch.cuda.is_available() (which `import librubiks`
+# calls) answers from that list instead of initialising the HIP runtime -- such a rank never opens the GPU, so a CPU test
+# of eight ranks on a GPU machine does not hold the card eight more times.
+CPU_ONLY_ENV = {"HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": "", "PYTORCH_NVML_BASED_CUDA_CHECK": "1"}
+# What that cannot prevent: torch calls that count the devices of every backend in C++, which on a ROCm build initialises the
+# HIP runtime and opens the GPU even when no device is visible -- dist.barrier() (hence `cpu_barrier`) and the autograd engine
+# before its first backward.  The GPU machines this suite runs on admit at most GPU_PROCESS_LIMIT processes per GPU.
+GPU_PROCESS_LIMIT = 6
+
+
+def cpu_barrier():
+    """dist.barrier() of CPU ranks: dist.barrier() first asks torch for the machine's accelerator, which on a GPU machine initialises
+    the HIP runtime and opens the GPU; an all_reduce of a CPU tensor waits for every rank the same way."""
+    import torch
+    import torch.distributed as dist
+    dist.all_reduce(torch.zeros(1))
+
+
+def skip_if_backward_ranks_exceed_the_gpu(world: int):
+    """For tests whose CPU ranks run backward: on a machine with a GPU, `world` ranks and this process all hold it."""
+    import pytest
+    import torch
+    if torch.cuda.is_available() and world + 1 > GPU_PROCESS_LIMIT:
+        pytest.skip(f"needs {world + 1} processes on one GPU (each rank's backward opens it), at most {GPU_PROCESS_LIMIT} may hold it")
+
+
+def run_ranks(target, world: int, make_args, timeout: float = 300.0, gpu: bool = True) -> list:
     """
     Runs target(*make_args(rank, port, q)) in `world` spawned processes; every rank puts exactly one result on q.
     Returns the sorted results.  Raises AssertionError as soon as a rank has died or reported an exception (with its
     traceback), or when `timeout` seconds have passed; all ranks are terminated before returning.
+    gpu=False: the ranks run on the CPU and do not see the GPU at all (CPU_ONLY_ENV).
     """
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
@@ -78,8 +105,18 @@ def run_ranks(target, world: int, make_args, timeout: float = 300.0) -> list:
 
     got, deadline = [], time.monotonic() + timeout
     try:
-        for p in procs:
-            p.start()
+        saved = {k: os.environ.get(k) for k in CPU_ONLY_ENV}
+        if not gpu:
+            os.environ.update(CPU_ONLY_ENV)      # a spawned child starts with the environment of this moment
+        try:
+            for p in procs:
+                p.start()
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
         while len(got) < world:
             try:
                 item = q.get(timeout=1.0)

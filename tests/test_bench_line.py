@@ -213,3 +213,18 @@ def test_launched_ranks_get_the_ipc_mode_rccl_needs_on_this_pool(monkeypatch, tm
     seen.clear()
     monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "1")
     assert bench.launch_ranks(2, ["--gpus", "2"]) == 0 and [e["HSA_ENABLE_IPC_MODE_LEGACY"] for e in seen] == ["1", "1"]
+
+
+def test_dump_outputs_writes_float_arrays_per_leg(tmp_path):
+    """--dump-outputs: one DIR/<leg>_<name>.npy per array (rank-prefixed under N ranks); float32 / float64 only."""
+    import numpy as np
+    arrays = {"tree_nodes": np.arange(4, dtype=np.float64), "net_values": np.linspace(0, 1, 6, dtype=np.float32)}
+    bench.write_outputs(str(tmp_path / "one"), "f32s", arrays, 0, 1)
+    assert sorted(os.listdir(tmp_path / "one")) == ["f32s_net_values.npy", "f32s_tree_nodes.npy"]
+    for key, arr in arrays.items():
+        back = np.load(tmp_path / "one" / f"f32s_{key}.npy")
+        assert back.dtype == arr.dtype and np.array_equal(back, arr)
+    bench.write_outputs(str(tmp_path / "two"), "bf16", arrays, 1, 2)
+    assert sorted(os.listdir(tmp_path / "two")) == ["rank1_bf16_net_values.npy", "rank1_bf16_tree_nodes.npy"]
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "bad"), "f32s", {"ints": np.arange(3)}, 0, 1)

@@ -43,7 +43,7 @@ def test_save_load_round_trip(tmp_path):
     _randomise_bn(m)
     m.save(str(tmp_path))
     m.save(str(tmp_path), is_min=True)
-    m2 = Model.load(str(tmp_path), load_best=True)
+    m2 = Model.load(str(tmp_path), load_best=True).cpu()     # (load places the model on the GPU when there is one)
     assert isinstance(m2.config.activation_function, torch.nn.ReLU)
     x = _one_hot(5)
     m.eval(), m2.eval()
@@ -150,7 +150,7 @@ def golden_model_inputs():
 def seeded_reference_model(arch, bn, fx=None, trained_stats=False):
     """The build's Model under the reference's seed; with `trained_stats` the BatchNorm statistics of the fixture loaded."""
     torch.manual_seed(0)
-    net = Model.create(ModelConfig(architecture=arch, batchnorm=bn))
+    net = Model.create(ModelConfig(architecture=arch, batchnorm=bn)).cpu()     # (create places it on the GPU when there is one)
     if trained_stats:
         pre = f"{arch}_bn1_stat_"
         net.load_state_dict({k[len(pre):]: torch.from_numpy(fx[k]) for k in fx.files if k.startswith(pre)}, strict=False)

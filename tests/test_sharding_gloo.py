@@ -7,7 +7,7 @@ import pytest
 import torch.distributed as dist
 
 from librubiks.solving.sharding import gather_results, shard_range, summarize
-from ranks import init_gloo, run_ranks
+from ranks import cpu_barrier, init_gloo, run_ranks, skip_if_backward_ranks_exceed_the_gpu
 
 
 def test_shard_range_covers_everything():
@@ -43,14 +43,14 @@ def _worker(rank, world, port, n_games, q):
     local = {"solved": (g % 3 == 0), "lengths": np.where(g % 3 == 0, g % 11, -1), "nodes": 100 + g}
     full = gather_results(local, n_games)
     q.put((rank, {k: v.tolist() for k, v in full.items()}, summarize(full, 2.0)))
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("n_games,world", [(37, 2), (37, 8), (5, 8)])
 def test_gather_of_uneven_shards(n_games, world):
     """Two ranks, the eight of a node (uneven shards), and more ranks than games (some shards are empty)."""
-    got = run_ranks(_worker, world, lambda r, port, q: (r, world, port, n_games, q), timeout=120)
+    got = run_ranks(_worker, world, lambda r, port, q: (r, world, port, n_games, q), timeout=120, gpu=False)
     g = np.arange(n_games)
     for rank, full, summary in got:
         assert full["nodes"] == (100 + g).tolist()
@@ -72,14 +72,14 @@ def _grad_worker(rank, world, port, q):
     local = [p.grad.clone() for p in net.parameters()]
     average_gradients(net)
     q.put((rank, [g.tolist() for g in local], [p.grad.tolist() for p in net.parameters()]))
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
 def test_data_parallel_gradient_average():
     """Config #4's only collective: the mean of per-rank gradients in one flat all_reduce."""
     world = 2
-    got = run_ranks(_grad_worker, world, lambda r, port, q: (r, world, port, q), timeout=120)
+    got = run_ranks(_grad_worker, world, lambda r, port, q: (r, world, port, q), timeout=120, gpu=False)
     mean = [np.mean([np.array(got[r][1][i]) for r in range(world)], axis=0) for i in range(len(got[0][1]))]
     for r in range(world):
         for i, m in enumerate(mean):
@@ -102,7 +102,7 @@ def _search_worker(rank, world, port, states, q):
     from librubiks.solving.sharding import sharded_search_batch
     got = sharded_search_batch(_ToyAgent(), states, None, 100)
     q.put((rank, {k: v.tolist() for k, v in got.items()}))
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -113,7 +113,7 @@ def test_sharded_search_batch_on_several_ranks(world, n_games):
     rng = np.random.default_rng(0)
     states = rng.integers(0, 24, size=(n_games, 20)).astype(np.int8)
     whole = sharded_search_batch(_ToyAgent(), states, None, 100)      # no process group: plain search
-    got = run_ranks(_search_worker, world, lambda r, port, q: (r, world, port, states, q), timeout=180)
+    got = run_ranks(_search_worker, world, lambda r, port, q: (r, world, port, states, q), timeout=180, gpu=False)
     assert len(got) == world
     for _, full in got:
         for k in ("solved", "lengths", "nodes"):
@@ -143,7 +143,7 @@ def _bucket_worker(rank, world, port, exchange, q):
                 for p in net.parameters() for f in [buckets.flats[buckets.bucket_of[p]]])
     q.put((rank, len(buckets.flats), views, out))
     buckets.close()
-    dist.barrier()
+    cpu_barrier()
     dist.destroy_process_group()
 
 
@@ -154,7 +154,8 @@ def test_bucketed_async_gradient_average(world, exchange):
     all_gather_into_tensor: what uses all xGMI links at once; three ranks: buckets padded to whole shards; eight: the rank count of a node,
     where "auto" picks this form on RCCL)."""
     import torch
-    got = run_ranks(_bucket_worker, world, lambda r, port, q: (r, world, port, exchange, q), timeout=120)
+    skip_if_backward_ranks_exceed_the_gpu(world)
+    got = run_ranks(_bucket_worker, world, lambda r, port, q: (r, world, port, exchange, q), timeout=120, gpu=False)
     assert got[0][1] == got[1][1] >= 3 and got[0][2] and got[1][2]
     for step in range(3):
         # reference: the same two local backward passes in this process, averaged by hand
@@ -194,7 +195,7 @@ def test_a_dead_rank_fails_the_test_quickly_with_its_output(how):
     import multiprocessing
     t0 = time.monotonic()
     with pytest.raises(AssertionError) as e:
-        run_ranks(_dying_worker, 2, lambda r, port, q: (r, 2, port, how, q), timeout=120)
+        run_ranks(_dying_worker, 2, lambda r, port, q: (r, 2, port, how, q), timeout=120, gpu=False)
     assert time.monotonic() - t0 < 15
     text = str(e.value)
     assert ("rank 1 gives up before the collective" in text and "Traceback" in text) if how == "raise" else \

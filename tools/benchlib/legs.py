@@ -33,13 +33,53 @@ def replay_solutions(roots_np, res, what):
     return {"games_reported_solved": int(len(idx)), "solutions_replayed_to_solved": ok}
 
 
-def run_leg(name, model, pool_roots, config_roots, args, world, coll_device, trees, cap, window_only=False, full_warm=True):
+DUMP_ROWS = 32      # node rows per tree in the output snapshot (rows 0 .. 31 of every tree: the root and its first children)
+DUMP_TREES = 1024   # trees in it at most (more slots: a fixed, seeded sample of them), ~7 MB per leg
+
+
+def _sample(n, k):
+    return np.arange(n) if n <= k else np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+
+
+def window_outputs(run):
+    """
+    What the timed steps computed, as of the last one: the arrays a caller of the search holds at that point (per-tree state,
+    the node statistics of the trees' first DUMP_ROWS rows, the network's outputs of the last step).  Outside every timed region.
+    Only rows a kernel has written are read (rows 0 .. n_nodes of a tree, all of them backed by memory); the others are NaN.
+    """
+    from librubiks.solving import mcts_device as md
+    forest = run.forest
+    torch.cuda.synchronize()
+    trees = _sample(forest.B, DUMP_TREES)
+    net_rows = _sample(md.ROWS * forest.B, md.ROWS * DUMP_TREES)   # row 11 i + j: the j-th new child of the i-th listed tree
+    n_nodes = forest.n_nodes.cpu().numpy().astype(np.int64)[trees]
+    r = np.arange(DUMP_ROWS)
+    valid = (r[None, :] <= n_nodes[:, None]) & (r[None, :] < forest.mapped_host[trees][:, None]) & (r[None, :] <= forest.C)
+    rows = (trees[:, None] * (forest.C + 1) + r[None, :])[valid]
+    idx = torch.from_numpy(rows).to(forest.device)
+    out = {"tree_status": forest.status, "tree_nodes": forest.n_nodes, "tree_iterations": forest.iterations, "tree_path_len": forest.path_len}
+    out = {k: v.cpu().numpy()[trees].astype(np.float64) for k, v in out.items()}
+    owner = np.asarray(run.owner)                  # game index of every slot (-1: empty)
+    out["slot_game"] = owner[_sample(len(owner), DUMP_TREES)].astype(np.float64)
+    for name in ("N", "W", "P", "V"):
+        vals = getattr(forest, name)[idx].cpu().numpy()
+        dt = np.float64 if vals.dtype.kind in "iu" else np.float32
+        full = np.full((len(trees), DUMP_ROWS) + vals.shape[1:], np.nan, dtype=dt)
+        full[valid] = vals
+        out[f"node_{name}"] = full
+    out["net_probs"] = forest.probs.cpu().numpy()[net_rows].astype(np.float32)
+    out["net_values"] = forest.values.cpu().numpy()[net_rows].astype(np.float32)
+    return out
+
+
+def run_leg(name, model, pool_roots, config_roots, args, world, coll_device, trees, cap, window_only=False, full_warm=True, dump=None):
     """
     One network precision: steady-state window of K steps on the continuously refilled pool, the whole pool to
     completion, and the first `trees` scrambles as one batch to completion (BASELINE configs[1] when trees = 1 024).
     window_only: stop after the timed window.  full_warm: the untimed warm-up of the run to completion is the same search run
     once before (every launch size's HIP graph is then in the forest's cache, as in any evaluator that searches more than one
     batch); otherwise 30 iterations (the first graph only; the others are captured inside the timed run).
+    dump: a dict that receives `window_outputs` of the timed window (None: nothing is kept).
     Returns (dict for the JSON line, engine, agent).
     """
     from librubiks.model import F32_SPLIT, InferenceNet, SplitF32Net
@@ -95,6 +135,8 @@ def run_leg(name, model, pool_roots, config_roots, args, world, coll_device, tre
     seconds = time.perf_counter() - t0
     nodes = run.nodes_now() - nodes0
     steps_done = run.it - it0
+    if dump is not None:
+        dump.update(window_outputs(run))
     status = run.forest.status.cpu().numpy()
     running_in_window = int(((status == 0) & (run.owner >= 0)).sum())
     plen = run.forest.path_len.cpu().numpy()
