@@ -294,7 +294,9 @@ int rc_adi_targets(const float *values, const uint8_t *child_solved, const uint8
                                  * agents.py:575-595; max_path is a resource bound the caller chooses, not a search parameter) */
 #define RC_MCTS_ROOT_SOLVED 4   /* the scramble itself is solved (agents.py:468) */
 #define RC_MCTS_CORRUPT 5       /* rc_mcts_complete_graph / rc_mcts_shorten met an index that does not name a node of the tree (1 .. n_nodes)
-                                 * in its hash table or neighbour rows: the rows are not this tree's data.  The tree is left as it is. */
+                                 * in its hash table or neighbour rows: the rows are not this tree's data.  The tree is left as it is.
+                                 * Also rc_mcts_copy_trees, in the destination, for a source tree with more nodes than the destination has
+                                 * rows per tree (n_nodes > capacity): nothing else of that tree is written. */
 
 typedef struct rc_mcts {
     uint32_t n_trees;    /* B */

@@ -60,6 +60,19 @@ constexpr u32 kNoAct = 15;
 //   ROOT_B  rows: children 10, 11; then the root's backup (agents.py:555-561) and the first descent
 // A solved child found by the root's expansion is only reported (status) when ROOT_B has completed the tree.
 constexpr int kPhaseNormal = 0, kPhaseRootA = 1, kPhaseRootB = 2, kPhaseMask = 15, kPhaseSolved = 16;
+// Why a tag can be wrong and the tree still exact.  The path number keeps 16 bits of the iteration count, so after 65 536 iterations
+// (time-only trees get there) a tag written 65 536 + k iterations ago reads as k old, and the ring slot it names (path number mod ring_k)
+// holds a NEWER line.  Line following trusts a tag for nothing but where to look; what it does rely on is
+//   (1) every ring line is a path the tree's current tenant walked, levels 0 .. ring_len - 1 with ring_len <= ring_levels: the node at
+//       level i + 1 is the neighbour of the node at level i through the action at level i (a neighbour entry never changes once set),
+//       and a plant clears ring_len, so no line of an earlier tenant survives;
+//   (2) the first level of a segment is accepted only if the line's node there is the node the walk stands at (`want`, lane 0); a
+//       later level only as the successor of the accepted level above it -- which the LW == 1 walk takes from the ring itself;
+//   (3) every level's decision is re-derived (walk record, or the node's rows with the exact loss counts) and must equal the line's action.
+// A stale, aliased or wrong tag (or a slot that holds another line) therefore only ends a segment early, and the sequential walk
+// decides from there.  What would break it: a ring line that is not a walked path of the current tenant (rings copied between trees,
+// kept across a plant, or a line whose nodes and actions are shifted against each other), or a line position / node index out of range
+// (lpos < ring_len is all that bounds the ring reads).  tests/test_store_edges_gpu.py plants the wrap and scrambles rings and tags.
 __device__ __forceinline__ u32 line_tag(u32 seq, int level, u32 act) { return (seq << 16) | ((u32)level << 4) | act; }
 // Tree served by workgroup `slot` (rc_mcts_t::active): -1 = nobody.  The tree's network rows are 11 slot .. 11 slot + 10.
 __device__ __forceinline__ int tree_of(const rc_mcts_t &m, u32 slot) { return m.active ? m.active[slot] : (int)slot; }
@@ -1461,11 +1474,18 @@ __global__ __launch_bounds__(kBlock) void k_mcts_shorten(rc_mcts_t m) {
 // else into a results-only forest (neighbour rows as a plain [rows][12] array).
 // HASH: the tree's hash table travels as it is (source and destination have the same capacity); otherwise the destination's table --
 // of its own size -- is rebuilt from the copied keys by k_mcts_rehash.
+// A tree with more nodes than the destination has rows per tree (the host sized the destination from a stale node count) is not
+// copied: its status becomes RC_MCTS_CORRUPT and nothing else of it is written (k_mcts_rehash skips it as well).
 template <bool FULL, bool HASH>
 __global__ __launch_bounds__(kBlock) void k_mcts_copy_trees(rc_mcts_t src, rc_mcts_t dst, const int *__restrict__ src_trees, u32 dst_first) {
     const u32 ts = (u32)src_trees[blockIdx.x], td = dst_first + blockIdx.x;
     const size_t sb = (size_t)ts * (src.capacity + 1), db = (size_t)td * (dst.capacity + 1);
-    const u32 rows = (u32)src.n_nodes[ts] + 1u;
+    const u32 n = (u32)src.n_nodes[ts];   // (a negative count is as far out of range as a large one)
+    if (n > dst.capacity || n > src.capacity) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) dst.status[td] = RC_MCTS_CORRUPT;
+        return;
+    }
+    const u32 rows = n + 1u;
     const u32 tid = blockIdx.y * kBlock + threadIdx.x, nt = gridDim.y * kBlock;
     const uint4 *skeys = reinterpret_cast<const uint4 *>(src.keys) + sb;
     uint4 *dkeys = reinterpret_cast<uint4 *>(dst.keys) + db;
@@ -1492,19 +1512,30 @@ __global__ __launch_bounds__(kBlock) void k_mcts_copy_trees(rc_mcts_t src, rc_mc
 
 // The hash table of trees dst_first .. of a forest, rebuilt from their keys (nodes 1 .. n_nodes, which the caller has just copied in from a
 // forest of another capacity): cleared, then every key claims the first free slot from its home (the order does not matter to a lookup).
-// One workgroup per tree.
+// One workgroup per tree.  A tree k_mcts_copy_trees did not copy (n_nodes > capacity) is left alone.  check_mcts guarantees
+// hash_size >= 2 (capacity + 1), so a probe meets a free slot within hash_size steps; one that does not (a table that is not what this
+// kernel has just cleared) stops there and marks the tree RC_MCTS_CORRUPT.
 __global__ __launch_bounds__(kBlock) void k_mcts_rehash(rc_mcts_t m, const rc_mcts_t src, const int *__restrict__ src_trees, u32 dst_first) {
     const u32 t = dst_first + blockIdx.x;
-    const int n = src.n_nodes[src_trees[blockIdx.x]];   // (the destination's per-tree words are copied by the host afterwards)
+    const u32 ts = (u32)src_trees[blockIdx.x];
+    const u32 n = (u32)src.n_nodes[ts];
+    if (n > m.capacity || n > src.capacity) return;   // (status written by k_mcts_copy_trees)
     int *tab = m.hash + (size_t)t * m.hash_size;
     uint4 *tab4 = reinterpret_cast<uint4 *>(tab);
     for (u32 i = threadIdx.x; i < m.hash_size / 4; i += kBlock) tab4[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     const uint4 *keys = reinterpret_cast<const uint4 *>(m.keys) + (size_t)t * (m.capacity + 1);
     const u32 mask = m.hash_size - 1;
-    for (int i = 1 + (int)threadIdx.x; i <= n; i += kBlock) {
+    for (u32 i = 1 + threadIdx.x; i <= n; i += kBlock) {
         u32 h = key_hash(keys[i]) & mask;
-        while (atomicCAS(&tab[h], 0, i) != 0) h = (h + 1) & mask;
+        u32 probes = 0;
+        while (atomicCAS(&tab[h], 0, (int)i) != 0) {
+            if (++probes >= m.hash_size) {
+                m.status[t] = RC_MCTS_CORRUPT;
+                break;
+            }
+            h = (h + 1) & mask;
+        }
     }
 }
 
@@ -1635,8 +1666,8 @@ int rc_mcts_copy_trees(const rc_mcts_t *src, const rc_mcts_t *dst, const int32_t
     if (n == 0) return RC_OK;
     RC_REQUIRE(src_trees != nullptr, RC_ERR_NULL);
     RC_REQUIRE(n <= src->n_trees && dst_first <= dst->n_trees && n <= dst->n_trees - dst_first, RC_ERR_RANGE);
-    // the destination may be a forest of another (smaller) capacity -- the caller has made sure the trees fit its rows (n_nodes <= capacity):
-    // the hash tables then differ in size and the destination's are rebuilt from the keys
+    // the destination may be a forest of another (smaller) capacity -- the hash tables then differ in size and the destination's are
+    // rebuilt from the keys.  A tree that does not fit its rows (n_nodes > capacity) ends RC_MCTS_CORRUPT there, uncopied (k_mcts_copy_trees).
     RC_REQUIRE((src->hash_size & 3u) == 0 && (dst->hash_size & 3u) == 0, RC_ERR_RANGE);
     RC_REQUIRE(src->keys != dst->keys, RC_ERR_RANGE);
     const bool same = src->capacity == dst->capacity && src->hash_size == dst->hash_size;

@@ -232,9 +232,7 @@ class MCTSForest:
             "hash": ((B, self.hash_size), torch.int32),
             "n_nodes": ((B,), torch.int32), "status": ((B,), torch.int32), "solved_idx": ((B,), torch.int32),
             "solved_action": ((B,), torch.int32), "iterations": ((B,), torch.int32), "path_len": ((B,), torch.int32),
-            "pending": ((B,), torch.int32),
-            "ring_node": ((B, RING_K, self.ring_levels), torch.int32), "ring_act": ((B, RING_K, self.ring_levels), torch.uint8),
-            "ring_len": ((B, RING_K), torch.int32), "phase": ((B,), torch.int32),
+            "pending": ((B,), torch.int32), "ring_len": ((B, RING_K), torch.int32), "phase": ((B,), torch.int32),
         }
         self._ranges = {}     # name -> (VmmArray, bytes per row) of the arrays mapped on demand
         if self.vmm:
@@ -275,6 +273,9 @@ class MCTSForest:
                 t = z(shape, dt)
             setattr(self, name, t)
         self._make_path_store(z)
+        # the ring lines last: a path store that fell back to one block has shortened them (rc_mcts_t::ring_levels is their stride)
+        for name, dt in (("ring_node", torch.int32), ("ring_act", torch.uint8)):
+            setattr(self, name, z(((1 if _results_only else B), RING_K, self.ring_levels), dt))
         # the reference's per-action node arrays (agents.py:421-427) are strided views of the 256-byte node records: one or two
         # adjacent cache lines per node for the kernels, the same [rows, 12] tensors for everything that inspects a tree
         for name, (lo, hi, dt) in _NODE_FIELDS.items():
@@ -297,7 +298,7 @@ class MCTSForest:
         self.probs = z((ROWS * B, N_ACT), torch.float32)     # static network outputs (graph capture)
         self.values = z((ROWS * B,), torch.float32)
         s = _McStruct()
-        s.n_trees, s.capacity, s.hash_size, s.max_path = B, C, self.hash_size, max_path
+        s.n_trees, s.capacity, s.hash_size, s.max_path = B, C, self.hash_size, self.max_path   # (as `_make_path_store` settled it)
         s.rows_per_tree = ROWS
         s.node_words = N_ACT if _results_only else NODE_WORDS
         s.ring_k = RING_K
@@ -555,7 +556,8 @@ class MCTSForest:
     def adopt(self, pos: int, other: "MCTSForest", trees: np.ndarray):
         """Copies the (finished) trees `trees` of `other` into this forest's slots pos .. pos + len(trees) - 1: what this kind
         of forest keeps of a tree (results-only: keys, neighbours, leaf flags, hash table and the per-tree words result
-        extraction reads), rows 0 .. n_nodes only."""
+        extraction reads), rows 0 .. n_nodes only.  A tree with more nodes than this forest has rows (a stale `nodes_seen` sized the
+        forest) is not copied: rc_mcts_copy_trees marks it RC_MCTS_CORRUPT, and result extraction raises on it."""
         trees = np.asarray(trees, dtype=np.int64)
         k = len(trees)
         assert other.path_block == self.path_block and (self.results_only or other.ring_levels == self.ring_levels)
@@ -567,11 +569,13 @@ class MCTSForest:
         self.ensure_rows(np.arange(pos, pos + k), n + 2)
         self.nodes_seen[pos:pos + k] = n
         idx = torch.from_numpy(trees.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
-        _hip.check(self.lib.rc_mcts_copy_trees(ctypes.byref(other.struct), ctypes.byref(self.struct), idx.data_ptr(), k, pos,
-                                               _hip.stream_ptr()), "rc_mcts_copy_trees")
         pick = idx.long()
+        # the per-tree words first: the copy kernel's verdict on a tree that does not fit this forest's rows (status RC_MCTS_CORRUPT:
+        # nodes_seen is a host copy and may be stale) is the last word
         for name in (_RESULT_TREE if self.results_only else _PER_TREE):
             getattr(self, name)[pos:pos + k] = getattr(other, name)[pick]
+        _hip.check(self.lib.rc_mcts_copy_trees(ctypes.byref(other.struct), ctypes.byref(self.struct), idx.data_ptr(), k, pos,
+                                               _hip.stream_ptr()), "rc_mcts_copy_trees")
         for name in (("path_act",) if self.results_only else ("path_node", "path_act")):   # block by block, for the trees that reach it
             src, dst = getattr(other, name), getattr(self, name)
             dst[0, pos:pos + k] = src[0, pick]

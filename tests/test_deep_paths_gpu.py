@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, golden_cases
+from mcts_lockstep import compare_tree as _compare_tree
 
 pytestmark = pytest.mark.gpu
 
@@ -41,18 +42,6 @@ def knobs(monkeypatch):
         monkeypatch.setattr(md, "PATH_BLOCK", block)
         monkeypatch.setattr(md, "RING_LEVELS", ring)
     return set_
-
-
-def _compare_tree(tree: dict, ref: dict, n: int):
-    assert tree["n"] == n
-    assert np.array_equal(tree["states"][1:n + 1], ref["states"][1:n + 1])
-    assert np.array_equal(tree["neighbors"][:n + 1], ref["neighbors"][:n + 1])
-    assert np.array_equal(tree["leaves"][1:n + 1], ref["leaves"][1:n + 1])
-    assert np.array_equal(tree["N"][:n + 1], ref["N"][:n + 1])
-    assert np.array_equal(tree["L"][:n + 1], ref["L"][:n + 1])
-    assert np.array_equal(tree["V"][1:n + 1], np.asarray(ref["V"][1:n + 1], dtype=np.float64))
-    assert np.array_equal(tree["W"][1:n + 1], ref["W"][1:n + 1])
-    assert np.allclose(tree["P"][1:n + 1], ref["P"][1:n + 1], rtol=0, atol=1e-6)
 
 
 @pytest.mark.parametrize("case", golden_cases(_G, "mcts_"))
