@@ -1,8 +1,9 @@
 """
 bench.py -- MCTS node expansions/sec on depth-20 scrambles (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W            # the headline alone
+    python bench.py --gpus 1 --steps K --warmup W --full     # and everything else this file measures
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 Workload (BASELINE.json configs[1]): 1 024 concurrent depth-20 MCTS trees per GPU (np.random.seed(0), the
 reference's scramble stream), MCTS c = 0.6 with graph search, max_states 175 000 (the reference's default,
@@ -23,22 +24,28 @@ barrier + synchronize on both sides, harvesting and refilling included:
 This is done once per network precision (a "leg"):
   f32s  fp32 accuracy on the f16 matrix cores (the reference's net runs in fp32, librubiks/model.py:131-141)  ->  `value`, `dtype`
   f32   the fp32 MFMA GEMM chain as is (window only)          bf16  the fast engine  ->  `legs.*`
-Each leg also reports (sum of len(agent) / wall seconds of the batched search):
-  pool_run           the whole pool searched to completion / its wall time (prep, window and tail included)
-  run_to_completion  BASELINE configs[1] itself: the first 1 024 scrambles as ONE batch, to completion, + solve rate
 Ranks own disjoint scramble slices (weak scaling); the only collectives are the barrier, the max/sum reductions
 of the result and one all_gather of per-game results.
-Further legs on the same line (`--extra-legs`): `astar` = BASELINE configs[2] (4 096 depth-20 scrambles, AStar lambda 0.2, N 100:
-K timed iterations + the solve run at max_states 175 000, phase times and the roofline of its dominant kernel) and `config5` =
-one GPU's share of BASELINE configs[4] (8 192 concurrent depth-24 trees: timed window + the 8 192 as one batch to completion).
-The scalars that summarise all of this are repeated in `config.results`.
 
-Also printed on the same JSON line:
-  roofline      dominant kernel of the headline leg's step = the first hidden GEMM (MFMA bound)
-  roofline_env  the hand-written environment kernels in isolation (HBM bound; multi_rotate is the north_star's
-                roofline target) at 2^14 .. 2^26 states
-  phases        per-phase milliseconds of one MCTS step (HIP events, eager replay of the same step)
-  cpu_baseline  the restated reference agent (oracle/, NumPy + torch CPU) on this box's host cores
+A plain run (no --full) does what the headline needs and no more: it sets up, runs the f32s leg's prep, warm-up and K timed
+steps, writes --dump-outputs, and prints the line.  With --dump-outputs it also runs the timed window of the f32 and bf16 legs,
+whose arrays the dump holds; nothing behind a window runs.  Everything else is measured with --full only:
+  value_spread       SPREAD_WINDOWS further windows of K steps right behind each timed one
+  pool_run           the whole pool searched to completion / its wall time (prep, window and tail included)
+  run_to_completion  BASELINE configs[1] itself: the first 1 024 scrambles as ONE batch, to completion, + solve rate
+                     (both SURVEY 8(d)(i): sum of len(agent) / wall seconds of the batched search)
+  the f32 and bf16 legs, with the same reports (f32: window only)
+  `--extra-legs`     `astar` = BASELINE configs[2] (4 096 depth-20 scrambles, AStar lambda 0.2, N 100: K timed iterations + the
+                     solve run at max_states 175 000, phase times and the roofline of its dominant kernel), `config5` = one GPU's
+                     share of BASELINE configs[4] (8 192 concurrent depth-24 trees: timed window + the 8 192 as one batch to
+                     completion), `adi` = BASELINE configs[3] (data generation of an ADI rollout)
+  roofline           dominant kernel of the headline leg's step = the first hidden GEMM (MFMA bound)
+  roofline_env       the hand-written environment kernels in isolation (HBM bound; multi_rotate is the north_star's
+                     roofline target) at 2^14 .. 2^26 states
+  phases             per-phase milliseconds of one MCTS step (HIP events, eager replay of the same step)
+  cpu_baseline       the restated reference agent (oracle/, NumPy + torch CPU) on the host's cores
+  efficiency         of an N-GPU run, against the value a one-GPU --full run of the same workload left next to this file
+The scalars that summarise all of this are repeated in `config.results` (null where a plain run did not measure them).
 
 This file owns the contract (arguments, what is timed, the JSON line's keys) and the cpu_baseline leg -- besides tests/ and smoke() the only
 importer of oracle/.  The pieces live in tools/benchlib/: kernels.py (per-kernel timings, rooflines), legs.py (the MCTS / A* / ADI legs),
@@ -165,6 +172,7 @@ def cpu_adi(model, games=64, depth=32):
 # pool in bf16, 14 100 at fp32 accuracy), so every POOL_STEPS_PER_FACTOR steps of warm-up and window get one more scramble per
 # slot, on top of the two of the prep and one in reserve.  Up to 5 000 steps that is the pool of 8 x slots as it always was.
 POOL_STEPS_PER_FACTOR = 1000
+FULL_LEGS = "f32s,f32:window,bf16"   # the legs of a --full run (and of a --dump-outputs run); the first is the headline
 
 
 def write_outputs(out_dir, leg, arrays, rank, world):
@@ -176,23 +184,29 @@ def write_outputs(out_dir, leg, arrays, rank, world):
         np.save(os.path.join(out_dir, f"{prefix}_{key}.npy"), arr)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--trees", type=int, default=1024, help="concurrent MCTS trees (slots) per GPU")
     ap.add_argument("--depth", type=int, default=20)
-    ap.add_argument("--legs", default="f32s,f32:window,bf16",
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: every leg of FULL_LEGS with its spread windows, pool tail, run "
+                         "to completion, phases and roofline, the extra legs, roofline_env, cpu_baseline and the scaling record.  Without "
+                         "it a run times the headline leg's window and nothing else (with --dump-outputs: the window of every leg whose "
+                         "arrays the dump holds)")
+    ap.add_argument("--legs", default=None,
                     help="network engines to measure; the FIRST one is the headline `value`: f32s = fp32 accuracy on the f16 matrix "
                          "cores (SplitF32Net), f32 = fp32 MFMA GEMMs (the reference's arithmetic as is), bf16 = the fast engine; "
-                         "`:window` = timed window only (no pool tail, no run to completion)")
+                         f"`:window` = timed window only (no pool tail, no run to completion).  Default: {FULL_LEGS} with --full or "
+                         f"--dump-outputs, else the headline leg {FULL_LEGS.split(',')[0]} alone")
     ap.add_argument("--scale-ref-value", type=float, default=float(os.environ.get("RUBIKS_SCALE_REF", 0)) or None,
                     help="the one-GPU `value` of this workload (or RUBIKS_SCALE_REF): `efficiency` of an N-GPU run = value / (N x it).  Without "
-                         "it the record a --gpus 1 run of the same checkout left next to bench.py is used, else efficiency is null -- the "
+                         "it a --full run uses the record a --gpus 1 --full run of the same checkout left next to bench.py, else efficiency is null -- the "
                          "line always carries value_per_gpu (= value / N), which is all a driver needs to compute the curve itself")
     ap.add_argument("--extra-legs", default="auto",
-                    help="auto = astar,config5,adi on one GPU; config5 alone under --gpus N > 1 (the curve needs the MCTS window, the run to "
+                    help="auto = none without --full; with it astar,config5,adi on one GPU, config5 alone under --gpus N > 1 (the curve needs the MCTS window, the run to "
                          "completion and the config-5 share: A* and ADI at two precisions on every rank add a minute of wall time and "
                          "nothing to it).  astar = BASELINE configs[2] (4 096 depth-20 A* problems per GPU); config5 = one GPU's share of configs[4] "
                          "(8 192 concurrent depth-24 trees); adi = configs[3] (data generation of a 16 384-state ADI rollout); none = "
@@ -206,10 +220,11 @@ def main():
     ap.add_argument("--pool-factor", type=int, default=None,
                     help="scrambles in the pool per tree slot (default: 8, more when --steps needs more, see POOL_STEPS_PER_FACTOR)")
     ap.add_argument("--prep-cap", type=int, default=4000, help="most untimed iterations before the timed window")
-    ap.add_argument("--window-only", action="store_true", help="skip the pool's tail and the runs to completion")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-env-roofline", action="store_true")
-    ap.add_argument("--phase-reps", type=int, default=20)
+    ap.add_argument("--window-only", action="store_true", help="with --full: skip the pool's tail and the runs to completion")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-env-roofline", action="store_true", help="with --full: no roofline_env")
+    ap.add_argument("--phase-reps", type=int, default=None, help="repetitions of the per-phase step timing after each leg (0: none; default 20 "
+                                                                 "with --full, else 0)")
     ap.add_argument("--weights", default=os.path.join(ROOT, "weights", "fc_small_r1"),
                     help="checkpoint directory (model.pt + config.json); random-init weights if it does not exist")
     ap.add_argument("--architecture", default="fc_small", choices=["fc_small", "fc_big", "res_small", "res_big"],
@@ -233,20 +248,36 @@ def main():
                          "window_outputs).  The inputs are seeded, so two builds run with the same arguments can be compared array for array")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="file that receives the full result (per-leg detail, phases, the roofline_env ladder); the stdout line names it")
-    args = ap.parse_args()
-    if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and not args.as_rank:
-        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))   # no launcher around us: start the ranks ourselves (before any HIP call)
+    return ap.parse_args(argv)
+
+
+def resolve(args):
+    """Fills in the defaults that depend on --full and the run's size; returns (legs, the legs measured to their window only, extra legs)."""
     if args.pool_factor is None:
         args.pool_factor = max(8, 3 + -(-(args.warmup + args.steps) // POOL_STEPS_PER_FACTOR))
     if args.level_budget != "auto":
         args.level_budget = int(args.level_budget)
+    if args.legs is None:   # --dump-outputs writes every default leg's arrays, with or without --full
+        args.legs = FULL_LEGS if args.full or args.dump_outputs else FULL_LEGS.split(",")[0]
+    if args.phase_reps is None:
+        args.phase_reps = 20 if args.full else 0
+    if not args.full:       # a plain run: the timed windows and nothing behind them
+        args.window_only = args.no_cpu_baseline = args.no_env_roofline = True
     legs = [x.split(":")[0] for x in args.legs.split(",") if x]
     leg_window_only = {x.split(":")[0]: x.endswith(":window") for x in args.legs.split(",") if x}
     assert legs and all(x in LEG_DTYPE for x in legs)
     if args.extra_legs == "auto":
-        args.extra_legs = "astar,config5,adi" if args.gpus == 1 else "config5"
+        args.extra_legs = "none" if not args.full else "astar,config5,adi" if args.gpus == 1 else "config5"
     extra = [] if args.extra_legs in ("", "none") else [x for x in args.extra_legs.split(",") if x]
     assert all(x in ("astar", "config5", "adi") for x in extra)
+    return legs, leg_window_only, extra
+
+
+def main():
+    args = parse_args()
+    if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and not args.as_rank:
+        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))   # no launcher around us: start the ranks ourselves (before any HIP call)
+    legs, leg_window_only, extra = resolve(args)
 
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -293,7 +324,8 @@ def main():
     for name in legs:
         dump = {} if args.dump_outputs else None
         leg, engine, agent = run_leg(name, model, pool_roots, config_roots, args, world, coll_device, args.trees, args.solve_max_states,
-                                     window_only=args.window_only or leg_window_only[name], full_warm=False, dump=dump)
+                                     window_only=args.window_only or leg_window_only[name], full_warm=False, dump=dump,
+                                     spread_windows=SPREAD_WINDOWS if args.full else 0)
         if leg["steps_timed"] != args.steps:     # ms_per_step is the time of one of exactly --steps steps, or there is no result
             sys.exit(f"bench: the '{name}' pool ran dry after {leg['steps_timed']} of the {args.steps} timed steps; raise --pool-factor")
         if dump:
@@ -323,7 +355,7 @@ def main():
         c_roots, c_pool = draw_scrambles(args.config5_trees, 3 * args.config5_trees, 24, slice_rank, slice_world)
         for name in ("f32s", "bf16"):
             leg, engine, agent = run_leg(name, model, c_pool, c_roots, args, world, coll_device, args.config5_trees, args.config5_max_states,
-                                         full_warm=False)
+                                         window_only=not args.full, full_warm=False, spread_windows=SPREAD_WINDOWS if args.full else 0)
             leg.pop("pool_run", None)   # the pool only feeds the window here (3 x 8 192 scrambles), its total is not a result
             config5[name] = leg
             if rank == 0:
@@ -396,8 +428,12 @@ def main():
     # of the same workload on the same checkout divides by it.  null when no such record exists (or the workload differs).
     workload_key = {"trees": args.trees, "depth": args.depth, "max_states": args.solve_max_states, "leg": legs[0], "pool_factor": args.pool_factor,
                     "steps": args.steps, "warmup": args.warmup}
-    efficiency, efficiency_note = scale_efficiency(world, head["value"], workload_key, os.path.join(ROOT, SCALE_REF), write=not args.as_rank,
-                                                   gpu=torch.cuda.get_device_name(device_index), ref_value=args.scale_ref_value)
+    if args.full or args.scale_ref_value:
+        efficiency, efficiency_note = scale_efficiency(world, head["value"], workload_key, os.path.join(ROOT, SCALE_REF),
+                                                       write=args.full and not args.as_rank, gpu=torch.cuda.get_device_name(device_index),
+                                                       ref_value=args.scale_ref_value)
+    else:   # a plain run neither leaves the record nor reads one an earlier run left
+        efficiency, efficiency_note = None, "not computed without --full (the one-GPU record) or --scale-ref-value"
     weights_short = os.path.relpath(args.weights, ROOT) if os.path.isdir(args.weights) else "random-init"
     result = {
         "metric": "MCTS node expansions/sec, depth-20 scrambles", "value": head["value"],

@@ -228,3 +228,23 @@ def test_dump_outputs_writes_float_arrays_per_leg(tmp_path):
     assert sorted(os.listdir(tmp_path / "two")) == ["rank1_bf16_net_values.npy", "rank1_bf16_tree_nodes.npy"]
     with pytest.raises(AssertionError):
         bench.write_outputs(str(tmp_path / "bad"), "f32s", {"ints": np.arange(3)}, 0, 1)
+
+
+def test_a_plain_run_measures_the_headline_window_alone():
+    """Without --full: the headline leg's timed window and nothing behind it; --dump-outputs adds the other legs' windows (the
+    dump holds their arrays); --full is every leg, extra leg and side measurement; options given explicitly hold either way."""
+    args = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.resolve(args) == (["f32s"], {"f32s": False}, [])
+    assert args.window_only and args.no_cpu_baseline and args.no_env_roofline and args.phase_reps == 0 and args.pool_factor == 8
+
+    args = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "out"])
+    legs, window, extra = bench.resolve(args)
+    assert legs == ["f32s", "f32", "bf16"] and extra == [] and args.window_only and args.phase_reps == 0
+
+    args = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.resolve(args) == (["f32s", "f32", "bf16"], {"f32s": False, "f32": True, "bf16": False}, ["astar", "config5", "adi"])
+    assert not (args.window_only or args.no_cpu_baseline or args.no_env_roofline) and args.phase_reps == 20
+    assert bench.resolve(bench.parse_args(["--gpus", "2", "--full"]))[2] == ["config5"]
+
+    args = bench.parse_args(["--legs", "bf16,f32s", "--extra-legs", "astar", "--phase-reps", "3"])
+    assert bench.resolve(args) == (["bf16", "f32s"], {"bf16": False, "f32s": False}, ["astar"]) and args.phase_reps == 3 and args.window_only

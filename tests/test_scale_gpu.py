@@ -135,7 +135,7 @@ def test_bench_two_ranks_aggregate_their_shares():
     shapes and bit-identical trees): the distributed results must be exactly the sum of the two.
     """
     import socket
-    common = ["--steps", "6", "--warmup", "2", "--trees", "48", "--pool-factor", "2", "--legs", "bf16", "--solve-max-states",
+    common = ["--full", "--steps", "6", "--warmup", "2", "--trees", "48", "--pool-factor", "2", "--legs", "bf16", "--solve-max-states",
               "1500", "--phase-reps", "0", "--no-cpu-baseline", "--no-env-roofline", "--prep-cap", "40", "--astar-problems", "24",
               "--config5-trees", "32", "--config5-max-states", "800", "--extra-legs", "astar,config5"]   # (N > 1 defaults to config5 alone)
     with socket.socket() as s:

@@ -18,8 +18,8 @@ O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 case $mode in
 bench)
-  rocprofv3 --kernel-trace --stats -d /tmp/prof_$tag -o bench -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --detail $O/${tag}_bench_detail_under_rocprof.json "$@" > $O/${tag}_bench_under_rocprof.json 2> $O/${tag}_bench_under_rocprof.err
-  python3 $R/tools/rocprof_summary.py kernels "$(find /tmp/prof_$tag -name '*.db' | head -1)" $O/${tag}_bench_kernel_stats.csv 100 ;;
+  rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_$tag -o bench -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --detail $O/${tag}_bench_detail_under_rocprof.json "$@" > $O/${tag}_bench_under_rocprof.json 2> $O/${tag}_bench_under_rocprof.err
+  python3 $R/tools/rocprof_summary.py kernels "$(find $TMPDIR/prof_$tag -name '*.db' | head -1)" $O/${tag}_bench_kernel_stats.csv 100 ;;
 timeline)
   dt=${1:-f32s}
   rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_tl_$tag -- python3 $R/tools/search_probe.py solve --dtype $dt --out $O/${tag}_solve_run_$dt.json > $O/${tag}_timeline.log 2>&1

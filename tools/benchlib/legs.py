@@ -72,11 +72,13 @@ def window_outputs(run):
     return out
 
 
-def run_leg(name, model, pool_roots, config_roots, args, world, coll_device, trees, cap, window_only=False, full_warm=True, dump=None):
+def run_leg(name, model, pool_roots, config_roots, args, world, coll_device, trees, cap, window_only=False, full_warm=True, dump=None,
+            spread_windows=SPREAD_WINDOWS):
     """
     One network precision: steady-state window of K steps on the continuously refilled pool, the whole pool to
     completion, and the first `trees` scrambles as one batch to completion (BASELINE configs[1] when trees = 1 024).
-    window_only: stop after the timed window.  full_warm: the untimed warm-up of the run to completion is the same search run
+    window_only: stop after the timed window and the `spread_windows` windows of K steps behind it (`value_spread`; 0: none, and
+    value_spread is None).  full_warm: the untimed warm-up of the run to completion is the same search run
     once before (every launch size's HIP graph is then in the forest's cache, as in any evaluator that searches more than one
     batch); otherwise 30 iterations (the first graph only; the others are captured inside the timed run).
     dump: a dict that receives `window_outputs` of the timed window (None: nothing is kept).
@@ -145,8 +147,8 @@ def run_leg(name, model, pool_roots, config_roots, args, world, coll_device, tre
     flushes_in_window = run.stats.get("flushes", 0) - flushes0
     # Five more windows of K steps right behind the timed one (same bracket): how far one K-step window of this run is from the next,
     # so that a change of a few per cent between two runs can be told from the window's own scatter (value_spread: median, min, max).
-    more = torch.zeros((SPREAD_WINDOWS, 2), dtype=torch.float64)
-    for w in range(SPREAD_WINDOWS):
+    more = torch.zeros((spread_windows, 2), dtype=torch.float64)
+    for w in range(spread_windows):
         over = torch.tensor([1.0 if run.done else 0.0], dtype=torch.float64, device=coll_device)
         if world > 1:      # every rank runs the same number of windows (each ends in a collective): stop together when any pool has run dry
             dist.all_reduce(over, op=dist.ReduceOp.MAX)
@@ -199,7 +201,7 @@ def run_leg(name, model, pool_roots, config_roots, args, world, coll_device, tre
                          dtype=torch.float64, device=coll_device)
     rank_values = [round(nodes / seconds, 1)]           # every rank's own window: its nodes / its seconds
     more = more.to(coll_device)
-    if world > 1:       # a window of the job: all ranks' nodes / the slowest rank's seconds
+    if world > 1 and spread_windows:       # a window of the job: all ranks' nodes / the slowest rank's seconds
         sec, nod = more[:, 0].clone(), more[:, 1].clone()
         dist.all_reduce(sec, op=dist.ReduceOp.MAX)
         dist.all_reduce(nod, op=dist.ReduceOp.SUM)
