@@ -6,6 +6,8 @@ Run only in the build container, where the reference is mounted read-only:
     cd /tmp && PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg PYTHONPATH=/root/reference \
         python /root/repo/tests/golden/make_golden.py [cube] [bfs] [bfs_cut] [agents] [adi] [simple] [model]
 
+`solve` (make_golden_solve.py, trained-weight MCTS / A* outcomes) runs only when named, like `model`.
+
 The fixtures are DATA (inputs + the reference's outputs).  No reference source travels with them.
 The GPU box never runs this script (it has no /root/reference); it only reads the committed files.
 """
@@ -225,3 +227,6 @@ if __name__ == "__main__":
         make_adi()
     if "model" in what:
         make_model()
+    if "solve" in what:
+        from make_golden_solve import make_solve
+        make_solve()
