@@ -510,6 +510,11 @@ int rc_vmm_dump(char *out, size_t cap, size_t *out_needed);
  * Node indices are 1-based per problem (index 0 unused, agents.py:189); arrays are problem-major
  * with capacity + 1 rows.  Device pointers, zero-initialised by the caller except `claim`, which
  * must be filled with INT32_MAX.
+ * Invariant: between iterations every `claim` row is INT32_MAX again -- the row that wins an election
+ * in rc_astar_pop_expand or rc_astar_push_relax releases it -- so a slot replanted by rc_astar_plant
+ * needs no claim rows rewritten.
+ * Continuous batching: after an iteration, rc_astar_solutions reads the finished problems' queues and
+ * rc_astar_plant restarts their slots from waiting scrambles; the other problems are not touched.
  */
 #define RC_ASTAR_RUNNING 0
 #define RC_ASTAR_SOLVED 1        /* a NEW state of the batch is the solved cube (agents.py:321-323) */
@@ -563,6 +568,25 @@ int rc_astar_gather_new(const rc_astar_t *a, const int32_t *new_offset, int8_t *
  * (agents.py:326-328,333-367).  values[new_offset[b] + i] belongs to new state i of problem b. */
 int rc_astar_push_relax(const rc_astar_t *a, const int32_t *new_offset, const float *values, double lambda,
                         rc_stream_t stream);
+/* Restarts listed problem slots of a running batch: for i < n, slot slots[i] (device int32 list) gets roots_soa column
+ * first_col + i as its root -- its hash row is cleared, then it holds exactly what rc_astar_init writes for a problem (node 1,
+ * G 0, open list (0, 1), counters, status incl. RC_ASTAR_ROOT_SOLVED, solved_idx -1).  A listed index outside
+ * 0 .. n_problems - 1 is skipped (nothing is written for it).  Pass the column, not a shifted pointer: the SoA's planes are
+ * 16-byte aligned only at column 0.  Needs stride >= first_col + n. */
+int rc_astar_plant(const rc_astar_t *a, const int32_t *slots, uint32_t n, const int8_t *roots_soa, size_t stride,
+                   size_t first_col, rc_stream_t stream);
+/* Action queues of the listed problems (device int32 list of n problem indices), the walk of agents.py:244-251 from
+ * solved_idx back to node 1: row i of the [n][width] byte table `queues` gets problem problems[i]'s queue in root-to-goal
+ * order, lengths[i] its length.  lengths[i]: 0 for RC_ASTAR_ROOT_SOLVED, RC_ASTAR_PATH_UNSOLVED for any other status but
+ * RC_ASTAR_SOLVED; a queue longer than `width` reports its length and leaves its row unwritten (read it again with a wider
+ * table).  Every index read from memory is checked against the problem's 1 .. n_nodes, and a walk ends within n_nodes steps:
+ * otherwise RC_ASTAR_PATH_CORRUPT (the rows are not this problem's), and RC_ASTAR_PATH_NO_PROBLEM for a listed index outside
+ * 0 .. n_problems - 1. */
+#define RC_ASTAR_PATH_UNSOLVED (-1)
+#define RC_ASTAR_PATH_CORRUPT (-2)
+#define RC_ASTAR_PATH_NO_PROBLEM (-3)
+int rc_astar_solutions(const rc_astar_t *a, const int32_t *problems, uint32_t n, uint8_t *queues, uint32_t width,
+                       int32_t *lengths, rc_stream_t stream);
 
 /* ---- breadth-first search (one problem per call sequence, GPU-wide levels) -----------------------
  *

@@ -93,15 +93,15 @@ __device__ int heap_pop(double *hc, int *hi, int &size) {
 }
 
 // ---- init ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_astar_init(rc_astar_t a, const u8 *__restrict__ roots, size_t stride) {
-    const u32 b = blockIdx.x * kBlock + threadIdx.x;
-    if (b >= a.n_problems) return;
+// What a fresh problem b holds: root = node 1 (roots column `col`) in the hash row, which the caller has cleared, G 0, the open
+// list (cost 0, index 1), counters, status, solved_idx.  rc_astar_init writes it for every problem, rc_astar_plant for listed slots.
+__device__ void astar_init_problem(const rc_astar_t &a, u32 b, const u8 *__restrict__ roots, size_t stride, size_t col) {
     AStarView v = view_of(a, b);
     u32 w[4] = {0, 0, 0, 0};
     bool solved = true;
 #pragma unroll
     for (int j = 0; j < kPlanes; ++j) {
-        const u32 code = roots[(size_t)j * stride + b] & 31u;
+        const u32 code = roots[(size_t)j * stride + col] & 31u;
         key_set(w, j, code);
         solved &= code == (u32)(u8)kTables.solved[j];
     }
@@ -120,6 +120,26 @@ __global__ __launch_bounds__(kBlock) void k_astar_init(rc_astar_t a, const u8 *_
     a.iterations[b] = 0;
     a.n_popped[b] = 0;
     a.new_count[b] = 0;
+}
+
+__global__ __launch_bounds__(kBlock) void k_astar_init(rc_astar_t a, const u8 *__restrict__ roots, size_t stride) {
+    const u32 b = blockIdx.x * kBlock + threadIdx.x;
+    if (b >= a.n_problems) return;
+    astar_init_problem(a, b, roots, stride, b);
+}
+
+// ---- plant: listed slots of a running batch restart from new roots.  One workgroup per listed slot ----------------
+// The hash row is cleared (16-byte stores; hash_size is a power of two >= 2 (capacity + 1), so a row is whole uint4s), then
+// the slot gets what k_astar_init writes.  Nothing else of the old tenant needs clearing: node rows are read only below
+// n_nodes, the per-iteration staging is written before it is read, and the claim rows are INT32_MAX at rest.
+__global__ __launch_bounds__(kBlock) void k_astar_plant(rc_astar_t a, const int *__restrict__ slots, const u8 *__restrict__ roots,
+                                                      size_t stride, size_t first_col) {
+    const int s = slots[blockIdx.x];
+    if (s < 0 || (u32)s >= a.n_problems) return;   // (the whole workgroup: nothing is written for a slot that does not exist)
+    uint4 *tab4 = reinterpret_cast<uint4 *>(a.hash + (size_t)s * a.hash_size);
+    for (u32 i = threadIdx.x; i < a.hash_size / 4; i += kBlock) tab4[i] = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    if (threadIdx.x == 0) astar_init_problem(a, (u32)s, roots, stride, first_col + blockIdx.x);
 }
 
 // ---- pop + expand + dedup + append (agents.py:236-313) --------------------------------------------
@@ -357,6 +377,49 @@ __global__ __launch_bounds__(kBlock) void k_astar_push_relax(rc_astar_t a, const
         if (v.row_tmp[r]) v.claim[v.popped[r / kA12]] = kIdle;
 }
 
+// ---- solutions: action queues of listed problems (agents.py:244-251).  One lane per listed problem -------------------------
+// The walk from solved_idx back to node 1 is read twice: once to count (and check), once to write the queue root-to-goal into
+// its row.  Every index read from memory must name a node of the problem (1 .. n_nodes), and a chain ends within n_nodes
+// steps; anything else is not this problem's data and is reported, never followed.
+__global__ __launch_bounds__(kBlock) void k_astar_solutions(rc_astar_t a, const int *__restrict__ problems, u32 n, u8 *__restrict__ queues,
+                                                          u32 width, int *__restrict__ lengths) {
+    const u32 i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int b = problems[i];
+    if (b < 0 || (u32)b >= a.n_problems) {
+        lengths[i] = RC_ASTAR_PATH_NO_PROBLEM;
+        return;
+    }
+    const int status = a.status[b];
+    if (status != RC_ASTAR_SOLVED) {
+        lengths[i] = status == RC_ASTAR_ROOT_SOLVED ? 0 : RC_ASTAR_PATH_UNSOLVED;
+        return;
+    }
+    const AStarView v = view_of(a, (u32)b);
+    const int nn = a.n_nodes[b], goal = a.solved_idx[b];
+    if (nn < 1 || (u32)nn > a.capacity || goal < 1 || goal > nn) {
+        lengths[i] = RC_ASTAR_PATH_CORRUPT;
+        return;
+    }
+    int len = 0;
+    for (int x = goal; x != 1; ++len) {
+        const int p = v.parents[x];
+        if (len >= nn || p < 1 || p > nn) {
+            lengths[i] = RC_ASTAR_PATH_CORRUPT;
+            return;
+        }
+        x = p;
+    }
+    lengths[i] = len;
+    if ((u32)len > width) return;   // the caller reads this queue again with a wider table
+    u8 *row = queues + (size_t)i * width;
+    int x = goal;
+    for (int k = len - 1; k >= 0; --k) {   // (the chain was checked above)
+        row[k] = v.parent_actions[x];
+        x = v.parents[x];
+    }
+}
+
 }  // namespace rubiks
 
 using namespace rubiks;
@@ -380,6 +443,29 @@ int rc_astar_init(const rc_astar_t *a, const int8_t *roots_soa, size_t stride, r
     RC_CHECK_SOA(roots_soa, a->n_problems, stride);
     hipLaunchKernelGGL(k_astar_init, dim3(grid_for(a->n_problems, kBlock, 1 << 30)), dim3(kBlock), 0, (hipStream_t)stream,
                        *a, (const u8 *)roots_soa, stride);
+    return launch_status();
+}
+
+int rc_astar_plant(const rc_astar_t *a, const int32_t *slots, uint32_t n, const int8_t *roots_soa, size_t stride,
+                   size_t first_col, rc_stream_t stream) {
+    if (int rc = check_astar(a)) return rc;
+    RC_REQUIRE(slots && roots_soa, RC_ERR_NULL);
+    RC_REQUIRE(aligned16(roots_soa) && (stride & 15u) == 0 && aligned16(a->hash), RC_ERR_ALIGN);
+    RC_REQUIRE(n <= a->n_problems && stride >= first_col + n, RC_ERR_RANGE);
+    if (n == 0) return RC_OK;
+    hipLaunchKernelGGL(k_astar_plant, dim3(n), dim3(kBlock), 0, (hipStream_t)stream, *a, (const int *)slots, (const u8 *)roots_soa,
+                       stride, first_col);
+    return launch_status();
+}
+
+int rc_astar_solutions(const rc_astar_t *a, const int32_t *problems, uint32_t n, uint8_t *queues, uint32_t width, int32_t *lengths,
+                       rc_stream_t stream) {
+    if (int rc = check_astar(a)) return rc;
+    RC_REQUIRE(problems && queues && lengths, RC_ERR_NULL);
+    RC_REQUIRE(width > 0, RC_ERR_RANGE);
+    if (n == 0) return RC_OK;
+    hipLaunchKernelGGL(k_astar_solutions, dim3(grid_for(n, kBlock, 1 << 30)), dim3(kBlock), 0, (hipStream_t)stream, *a,
+                       (const int *)problems, n, queues, width, (int *)lengths);
     return launch_status();
 }
 

@@ -903,57 +903,117 @@ class AStar(DeepAgent):
 
     @no_grad
     def search_batch(self, states, time_limit: float = None, max_states: int = None,
-                     max_iterations: int = None) -> BatchResult:
+                     max_iterations: int = None, slots: int = None) -> BatchResult:
+        """
+        One A* problem per row of `states` ((G,20) int8 NumPy array or DeviceCubes).  `max_states` is the reference's per-problem
+        cap (stop when len + 12 N > max_states); `time_limit` bounds the wall time of the whole search; `max_iterations` bounds
+        every problem's number of iterations (plain batches only).
+        slots: search at most this many problems at a time and give the slots of finished problems to the scrambles still
+        waiting (continuous batching, as `MCTS.search_batch`): after an iteration's status read, the finished slots' queues are
+        walked on the device (rc_astar_solutions) and copied out without waiting, then the waiting scrambles are planted there
+        (rc_astar_plant).  Problems are independent, so a game's search is that of a plain batch wherever the network's values do
+        not depend on the batch (deterministic=True).  Games that never got a slot before the time limit end unsolved, with 0
+        nodes, status EXHAUSTED and 0 seconds.
+        """
         time_limit, max_states = self.reset(time_limit, max_states)
         roots = states if isinstance(states, DeviceCubes) else DeviceCubes.from_numpy(np.asarray(states))
-        cap_states = int(max_states) if max_states < int(1e10) else astar_time_only_capacity(roots.n)
-        batch = self._batch_for(roots.n, max(cap_states, 12 * self.expansions + 1))
+        n_games = roots.n
+        S = n_games if slots is None else max(1, min(int(slots), n_games))
+        if max_iterations is not None and S < n_games:
+            raise ValueError("max_iterations applies to plain batches only (slots >= number of games)")
+        cap_states = int(max_states) if max_states < int(1e10) else astar_time_only_capacity(S)
+        batch = self._batch_for(S, max(cap_states, 12 * self.expansions + 1))
+        self._arrays = None
         self.tt.tick()
-        batch.reset(roots)
-        it = 0
-        t_end = np.full(roots.n, np.nan)
+        batch.reset(roots)                          # the first S scrambles; the others move in as problems finish
+        owner = np.arange(S)                        # game of every slot; -1 once its result is taken and nobody moved in
+        planted_at = np.zeros(S, dtype=np.int64)    # loop iteration at which the slot's problem was planted
+        t_start, t_end = np.zeros(n_games), np.full(n_games, np.nan)
+        next_game, it, taken = S, 0, []             # taken: (games, pinned copies, event) of extracted slots
         while max_iterations is None or it < max_iterations:
             batch.iteration(self.lambda_, cap_states)
             it += 1
-            running = (batch.status == ad.RUNNING).cpu().numpy()      # (the loop synchronises here anyway: any_running)
+            status = batch.status.cpu().numpy()     # (the loop synchronises here anyway)
             now = self.tt.tock()
-            t_end[np.isnan(t_end) & ~running] = now                   # first sighting of a finished problem
-            if not running.any() or now >= time_limit:
+            live = owner >= 0
+            ended = live & (status != ad.RUNNING)
+            g = owner[ended]
+            t_end[g[np.isnan(t_end[g])]] = now      # first sighting of a finished problem
+            waiting = next_game < n_games
+            if now >= time_limit or not (live & ~ended).any() and not waiting:
                 break
+            done = np.flatnonzero(ended)
+            if waiting and len(done):
+                # a queue is no longer than its problem's G at the goal, and G <= the iterations since the plant (G[parent] + 1,
+                # relaxations only lower it, children are appended one iteration after their parent): this width always fits
+                width = int(max(1, (it - planted_at[done]).max()))
+                taken.append(self._take(batch, done, owner[done].copy(), width))
+                if 0 in owner[done]:
+                    self._arrays = batch.problem_arrays(int(np.flatnonzero(owner == 0)[0]))   # game 0 stays inspectable
+                k = min(len(done), n_games - next_game)
+                batch.plant(_to_device_async(done[:k].astype(np.int32), batch.device), roots, next_game)
+                owner[done] = -1
+                owner[done[:k]] = np.arange(next_game, next_game + k)
+                planted_at[done[:k]] = it
+                t_start[next_game:next_game + k] = self.tt.tock()
+                next_game += k
         torch.cuda.synchronize()
         if self._overflowed(batch.engine):   # the split engine could not represent an activation: the same search in fp32
             return self.search_batch(roots, time_limit if time_limit < 1e10 else None, max_states if max_states < int(1e10) else None,
-                                     max_iterations)
+                                     max_iterations, slots)
         seconds = self.tt.tock()
-        status = batch.status.cpu().numpy()
-        nodes = batch.n_nodes.cpu().numpy().astype(np.int64)
+        left = np.flatnonzero(owner >= 0)
+        parts = [self._result(*t) for t in taken]
+        if len(left):
+            status, nodes, iters = (x[torch.as_tensor(left, device=batch.device)].cpu().numpy().astype(np.int64)
+                                    for x in (batch.status, batch.n_nodes, batch.iterations))
+            lens, queues = batch.solutions(left)
+            parts.append((owner[left], self._part(status, nodes, iters, lens, queues)))
+        result = BatchResult.merge(n_games, parts, seconds)
+        if next_game < n_games:   # games that never got a slot before the time limit: unsolved, nothing explored
+            result.status[next_game:] = ad.EXHAUSTED
+            t_start[next_game:] = seconds
+        result.game_seconds = np.where(np.isnan(t_end), seconds, t_end) - t_start   # (still running at the end: until the end)
+        self._explored_states = int(result.nodes[0])
+        self.action_queue = result.queues[0]
+        return result
+
+    @staticmethod
+    def _take(batch, slots: np.ndarray, games: np.ndarray, width: int):
+        """Result extraction of the finished `slots` before they are replanted: queues walked on the device, then status, nodes,
+        iterations, lengths and queues copied into pinned memory on the current stream (nothing waits; `_result` reads them)."""
+        idx = _to_device_async(slots.astype(np.int32), batch.device)
+        table, lengths = batch.solutions_launch(idx, width)
+        pick = idx.long()
+        words = torch.stack([batch.status[pick], batch.n_nodes[pick], batch.iterations[pick], lengths])
+        host = (torch.empty(words.shape, dtype=words.dtype, pin_memory=True), torch.empty(table.shape, dtype=table.dtype, pin_memory=True))
+        host[0].copy_(words, non_blocking=True)
+        host[1].copy_(table, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return games, host, ev, (idx, table, words)   # (the device tensors live until the copies have landed)
+
+    @staticmethod
+    def _part(status, nodes, iters, lens, queues) -> BatchResult:
         solved = (status == ad.SOLVED) | (status == ad.ROOT_SOLVED)
-        sol_idx = batch.solved_idx.cpu().numpy()
-        queues = []
-        for b in range(batch.B):
-            q = deque()
-            if status[b] == ad.SOLVED:   # walk the parent pointers back to the root (agents.py:244-251)
-                lo = b * (batch.C + 1)
-                par = batch.parents[lo:lo + nodes[b] + 1].cpu().numpy()
-                pact = batch.parent_actions[lo:lo + nodes[b] + 1].cpu().numpy()
-                i = int(sol_idx[b])
-                while i != 1:
-                    q.appendleft(int(pact[i]))
-                    i = int(par[i])
-            queues.append(q)
-        lengths = np.array([len(q) if s else -1 for q, s in zip(queues, solved)])
-        self._explored_states = int(nodes[0])
-        self.action_queue = queues[0]
-        self._arrays = None
-        return BatchResult(solved, lengths, nodes, queues, seconds, batch.iterations.cpu().numpy(), status,
-                           np.where(np.isnan(t_end), seconds, t_end))
+        return BatchResult(solved, np.where(solved, lens, -1), nodes, queues, 0.0, iters, status)
+
+    def _result(self, games, host, ev, _keep):
+        ev.synchronize()
+        status, nodes, iters, lens = host[0].numpy().astype(np.int64)
+        ad.check_lengths(lens, games, "game")
+        acts = host[1].numpy().copy()
+        if (lens > acts.shape[1]).any():   # (cannot happen: see the width in search_batch)
+            raise _hip.RubiksHipError(f"A* solution extraction: game {int(games[np.argmax(lens > acts.shape[1])])}'s queue is longer "
+                                      f"than its iterations allow")
+        return games, self._part(status, nodes, iters, lens, QueueTable(acts, np.maximum(lens, 0)))
 
     def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
         return bool(self.search_batch(np.asarray(state)[None], time_limit, max_states).solved[0])
 
     # ---- inspectable attributes relied on by the reference's tests (tests/test_agents.py:110-145) ----
     def _host(self):
-        if self._arrays is None:
+        if self._arrays is None:   # (a pooled search snapshots game 0 before its slot is replanted)
             self._arrays = self.batch.problem_arrays(0)
         return self._arrays
 

@@ -20,6 +20,7 @@ from librubiks.model import make_inference_net, net_fingerprint
 from librubiks.solving.mcts_device import unpack_keys
 
 RUNNING, SOLVED, EXHAUSTED, OPEN_EMPTY, ROOT_SOLVED = 0, 1, 2, 3, 4
+PATH_UNSOLVED, PATH_CORRUPT, PATH_NO_PROBLEM = -1, -2, -3    # rc_astar_solutions' negative lengths
 N_ACT = 12
 INT_MAX = 2 ** 31 - 1
 
@@ -37,6 +38,8 @@ _hip.register({
     "rc_astar_pop_expand": [POINTER(_AsStruct), c_uint32, c_void_p],
     "rc_astar_gather_new": [POINTER(_AsStruct), c_void_p, c_void_p, c_size_t, c_void_p],
     "rc_astar_push_relax": [POINTER(_AsStruct), c_void_p, c_void_p, c_double, c_void_p],
+    "rc_astar_plant": [POINTER(_AsStruct), c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_void_p],
+    "rc_astar_solutions": [POINTER(_AsStruct), c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p],
 })
 
 NET_CHUNK = 1 << 19   # rows per network call (bounds the one-hot buffer to ~0.5 GB in bf16)
@@ -95,11 +98,50 @@ class AStarBatch:
             self._oh = torch.empty((rows, 480), dtype=self.engine.input_dtype, device=self.device)
 
     def reset(self, roots: DeviceCubes):
-        assert roots.n == self.B and self.engine is not None
+        """Every problem b starts from roots[b] (roots may hold more scrambles: the rest wait for `plant`)."""
+        assert roots.n >= self.B and self.engine is not None
         self.hash.zero_()
         self.claim.fill_(INT_MAX)
         _hip.check(self.lib.rc_astar_init(ctypes.byref(self.struct), roots.soa.data_ptr(), roots.stride, _hip.stream_ptr()),
                    "rc_astar_init")
+
+    def plant(self, slots: torch.Tensor, roots: DeviceCubes, first: int):
+        """Problem slots `slots` (int32 device tensor) restart from roots[first], roots[first + 1], ...; the others are not
+        touched, so finished problems of a running batch hand their slots to waiting scrambles between two iterations."""
+        assert slots.dtype == torch.int32 and slots.is_cuda and slots.is_contiguous() and first + slots.numel() <= roots.n
+        _hip.check(self.lib.rc_astar_plant(ctypes.byref(self.struct), slots.data_ptr(), int(slots.numel()), roots.soa.data_ptr(),
+                                           roots.stride, int(first), _hip.stream_ptr()), "rc_astar_plant")
+
+    def solutions_launch(self, problems: torch.Tensor, width: int):
+        """Queues rc_astar_solutions for `problems` (int32 device tensor): (uint8 [n, width] queue table, int32 [n] lengths),
+        device tensors on the current stream -- nothing waits."""
+        n = int(problems.numel())
+        assert problems.dtype == torch.int32 and problems.is_cuda and problems.is_contiguous() and width > 0
+        table = torch.empty((n, width), dtype=torch.uint8, device=self.device)
+        lengths = torch.empty(n, dtype=torch.int32, device=self.device)
+        _hip.check(self.lib.rc_astar_solutions(ctypes.byref(self.struct), problems.data_ptr(), n, table.data_ptr(), int(width),
+                                               lengths.data_ptr(), _hip.stream_ptr()), "rc_astar_solutions")
+        return table, lengths
+
+    def solutions(self, problems, width: int = 64):
+        """(int64 lengths, QueueTable) of `problems` (sequence of problem indices): the queues walked on the device
+        (rc_astar_solutions); a queue longer than `width` is read again with a table as wide as the longest.  Length -1 =
+        unsolved (empty queue).  Raises if a walk met indices that are not the problem's (synchronises)."""
+        from librubiks.solving.agents import QueueTable
+        idx = torch.as_tensor(np.asarray(problems, dtype=np.int32), device=self.device)
+        table, lengths = self.solutions_launch(idx, width)
+        lens = lengths.cpu().numpy().astype(np.int64)
+        acts = table.cpu().numpy()
+        check_lengths(lens, np.asarray(problems))
+        long = np.flatnonzero(lens > width)
+        if len(long):
+            table2, lengths2 = self.solutions_launch(idx[torch.as_tensor(long, device=self.device)], int(lens[long].max()))
+            acts2 = table2.cpu().numpy()
+            assert np.array_equal(lengths2.cpu().numpy(), lens[long])
+        queues = QueueTable(acts, np.maximum(lens, 0))
+        for o, i in enumerate(long):
+            queues.set_row(int(i), acts2[o, :lens[i]])
+        return lens, queues
 
     def _values_of_new(self, total: int):
         """Value head on the `total` compacted new states, chunked through the one-hot buffer."""
@@ -149,3 +191,12 @@ class AStarBatch:
             "open_queue": list(zip(self.heap_cost[lo:lo + hs].cpu().numpy().tolist(),
                                    self.heap_idx[lo:lo + hs].cpu().numpy().tolist())),
         }
+
+
+def check_lengths(lens: np.ndarray, who, what: str = "problem"):
+    """Raises if rc_astar_solutions reported rows that are not a problem's own (or a problem index outside the batch)."""
+    bad = np.flatnonzero(lens < PATH_UNSOLVED)
+    if len(bad):
+        i = int(bad[0])
+        why = "is not a slot of the batch" if lens[i] == PATH_NO_PROBLEM else "has parent pointers that leave its nodes (1 .. n_nodes)"
+        raise _hip.RubiksHipError(f"A* solution extraction: {len(bad)} queue(s) could not be read; first: {what} {int(np.asarray(who)[i])} {why}")

@@ -63,7 +63,8 @@ def sharded_search_batch(agent, states: np.ndarray, time_limit=None, max_states=
     ranks of the default process group: rank r runs agent.search_batch on its contiguous slice, then the per-game
     vectors are all-gathered.  Returns {"solved", "lengths", "nodes", "seconds"} for all n games, in game order, on every rank
     ("seconds": every game's own wall interval on its rank, `BatchResult.game_seconds`).
-    With a single process this is agent.search_batch on everything.
+    With a single process this is agent.search_batch on everything.  `kwargs` go to every rank's search_batch as they are
+    (e.g. slots=S for MCTS and AStar: each rank's slice is then searched on S slots).
     """
     states = np.asarray(states)
     world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1

@@ -1,6 +1,6 @@
 """
 The reference's evaluation protocol at its CLI defaults (runeval.py:32-73: 500 games per depth, max_states 175 000,
-MCTS c = 0.6 with graph search / AStar lambda 0.2 N 100) on one MI355X, all depths pooled on 1 024 concurrent trees.
+MCTS c = 0.6 with graph search / AStar lambda 0.2 N 100) on one MI355X, all depths pooled on 1 024 concurrent trees / A* problems.
 Writes the reference's result files (<out>/evaluation_results/*.npy, eval_settings.json) and a summary JSON.
 
     python tools/eval_default.py --out gpurun_out/eval_default
@@ -42,7 +42,7 @@ def main():
         if name == "mcts":
             agent, ev = MCTS(model, c=0.6, search_graph=True, net_dtype=nd), Evaluator(args.games, depths, None, args.max_states, slots=args.slots)
         else:
-            agent, ev = AStar(model, lambda_=0.2, expansions=100, net_dtype=nd), Evaluator(args.games, depths, None, args.max_states)
+            agent, ev = AStar(model, lambda_=0.2, expansions=100, net_dtype=nd), Evaluator(args.games, depths, None, args.max_states, slots=args.slots)
         torch.cuda.synchronize()
         t = time.perf_counter()
         res, states, times = ev.eval(agent)
