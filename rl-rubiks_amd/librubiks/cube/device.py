@@ -50,6 +50,11 @@ class DeviceCubes:
         return cls.from_aos(torch.from_numpy(states).cuda())
 
     @classmethod
+    def of(cls, states) -> "DeviceCubes":
+        """`states` as they are if they live on the device already, else uploaded from an (n,20) host array."""
+        return states if isinstance(states, cls) else cls.from_numpy(np.asarray(states))
+
+    @classmethod
     def from_aos(cls, aos: torch.Tensor) -> "DeviceCubes":
         lib = _hip.lib()
         n = aos.shape[0]

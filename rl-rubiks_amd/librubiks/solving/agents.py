@@ -24,6 +24,7 @@ from librubiks.model import F32_SPLIT, F32_SPLIT_DET, Model, net_fingerprint
 from librubiks.solving import astar_device as ad
 from librubiks.solving import bfs_device as bd
 from librubiks.solving import mcts_device as md
+from librubiks.solving.results import BatchResult, QueueTable   # noqa: F401  (also this module's names: callers import them from here)
 from librubiks.utils import TickTock
 
 DEFAULT_NODE_CAP = 1 << 18   # least per-tree / per-problem node capacity of a search bounded by time only
@@ -70,17 +71,27 @@ class Agent:
         return self._explored_states
 
 
+def _unbounded(limit) -> bool:
+    """True for what `Agent.reset` returns in place of a limit that was not given: the search is bounded by the other one alone."""
+    return limit >= 1e10
+
+
 class DeepAgent(Agent):
     """
     Agents that evaluate a network.  `net_dtype` selects the inference engine (librubiks.model.make_inference_net): the default
     F32_SPLIT is the reference's precision (its forward is fp32, agents.py:551-552) on the f16 matrix cores; torch.bfloat16 is the
-    fast engine, torch.float32 the plain fp32 GEMM chain.
+    fast engine, torch.float32 the plain fp32 GEMM chain; `deterministic=True` asks for the split engine's one-plan form (see `MCTS`).
     """
-    net_dtype = F32_SPLIT
 
-    def __init__(self, net):
+    def __init__(self, net, net_dtype=F32_SPLIT, deterministic: bool = False):
         super().__init__()
-        self.net = net
+        if deterministic:
+            if net_dtype not in (F32_SPLIT, F32_SPLIT_DET):
+                raise ValueError("deterministic=True runs on the split engine (net_dtype=F32_SPLIT): the library GEMMs of the other engines "
+                                 "choose their kernels by batch shape")
+            net_dtype = F32_SPLIT_DET
+        self.net, self.net_dtype = net, net_dtype
+        self.deterministic = net_dtype == F32_SPLIT_DET
         self._fp32_for = None   # (fingerprint of `net`, fp32 engine) once a search on the split engine left half range
 
     def _search_net(self):
@@ -106,120 +117,6 @@ class DeepAgent(Agent):
         return cls(Model.load(loc, load_best=use_best).to(gpu), **kwargs)
 
 
-class QueueTable:
-    """
-    Action queues of a batch kept as rows of a (games, max_len) uint8 array plus a length per game; a
-    `deque` of ints is only built for the games somebody indexes (`table[g]`, iteration).  Behaves like
-    the list of deques it replaces.
-    """
-
-    def __init__(self, acts: np.ndarray = None, lens: np.ndarray = None, n: int = None):
-        if acts is not None:
-            self._rows = [(acts, i) for i in range(len(lens))]
-            self._lens = np.asarray(lens, dtype=np.int64).copy()
-        else:
-            self._rows = [None] * n
-            self._lens = np.zeros(n, dtype=np.int64)
-
-    def put(self, g: int, other: "QueueTable", i: int):
-        self._rows[g], self._lens[g] = other._rows[i], other._lens[i]
-
-    def set_row(self, g: int, acts: np.ndarray):
-        """Game g's queue from an array of its own (a queue longer than the rows of the shared array)."""
-        arr = np.ascontiguousarray(acts, dtype=np.uint8).reshape(1, -1)
-        self._rows[g], self._lens[g] = (arr, 0), arr.shape[1]
-
-    def lengths(self) -> np.ndarray:
-        return self._lens
-
-    def padded(self, games=None, fill: int = 255):
-        """(uint8 [len(games), longest] array of the games' action queues padded with `fill`, their lengths): the queues of many
-        games at once without building a deque per game (replaying / scoring whole result sets)."""
-        games = np.arange(len(self)) if games is None else np.asarray(games, dtype=np.int64)
-        lens = self._lens[games]
-        out = np.full((len(games), int(lens.max()) if len(games) else 0), fill, dtype=np.uint8)
-        for o, g in enumerate(games):
-            src = self._rows[g]
-            if src is not None and lens[o]:
-                out[o, :lens[o]] = src[0][src[1], :lens[o]]
-        return out, lens
-
-    def __len__(self):
-        return len(self._rows)
-
-    def __getitem__(self, g):
-        if isinstance(g, slice):
-            return [self[i] for i in range(*g.indices(len(self)))]
-        src = self._rows[g]
-        if src is None:
-            return deque()
-        acts, i = src
-        return deque(int(a) for a in acts[i, :self._lens[g]])
-
-    def __setitem__(self, g, q):
-        if isinstance(g, slice):
-            for i, qq in zip(range(*g.indices(len(self))), q):
-                self[i] = qq
-            return
-        arr = np.fromiter(q, dtype=np.uint8, count=len(q)).reshape(1, -1)
-        self._rows[g], self._lens[g] = (arr, 0), len(q)
-
-    def __iter__(self):
-        return (self[g] for g in range(len(self)))
-
-
-class BatchResult:
-    """Per-scramble outcome of a batched search (shapes (B,)); `queues[t]` is tree t's action queue."""
-
-    def __init__(self, solved, lengths, nodes, queues, seconds, iterations, status, game_seconds=None):
-        self.solved, self.lengths, self.nodes, self.queues = solved, lengths, nodes, queues
-        self.seconds, self.iterations, self.status = seconds, iterations, status
-        # Per-game wall interval (float64 [B]) where the agent keeps one: from the moment the game's search starts (its tree is
-        # planted / its problem enters the batch) to the moment the host sees it finished -- what the reference's Evaluator times
-        # around agent.search (evaluation.py:45-52).  Games of one batch share the GPU, so these intervals OVERLAP: their sum is not
-        # the batch's wall time (`seconds`).  None: the agent does not record them.
-        self.game_seconds = game_seconds
-
-    @property
-    def states_per_sec(self) -> float:
-        return float(self.nodes.sum()) / max(self.seconds, 1e-12)
-
-    @property
-    def path_overflow_trees(self) -> int:
-        """Trees that ended because a descent filled the path store (status PATH_OVERFLOW).  The reference has no such limit
-        (agents.py:575-595): with the default store (MCTS(max_path=None)) this is HBM / address space running out and is 0 in
-        every run on record; a caller who bounds the store (max_path=...) reads here what that bound cost."""
-        return int((np.asarray(self.status) == md.PATH_OVERFLOW).sum())
-
-    def select(self, mask: np.ndarray) -> "BatchResult":
-        idx = np.flatnonzero(mask)
-        if isinstance(self.queues, QueueTable):
-            queues = QueueTable(n=len(idx))
-            for o, i in enumerate(idx):
-                queues.put(o, self.queues, int(i))
-        else:
-            queues = [self.queues[i] for i in idx]
-        return BatchResult(self.solved[idx], self.lengths[idx], self.nodes[idx], queues,
-                           self.seconds, self.iterations[idx], self.status[idx],
-                           None if self.game_seconds is None else self.game_seconds[idx])
-
-    @staticmethod
-    def merge(n: int, parts, seconds: float) -> "BatchResult":
-        """Reassembles per-game results from (original indices, BatchResult) pieces."""
-        solved, lengths = np.zeros(n, dtype=bool), np.full(n, -1, dtype=np.int64)
-        nodes, iters, status = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-        queues = QueueTable(n=n)
-        for owner, r in parts:
-            solved[owner], lengths[owner], nodes[owner] = r.solved, r.lengths, r.nodes
-            iters[owner], status[owner] = r.iterations, r.status
-            for i, o in enumerate(owner):
-                if isinstance(r.queues, QueueTable):
-                    queues.put(int(o), r.queues, i)
-                else:
-                    queues[int(o)] = r.queues[i]
-        return BatchResult(solved, lengths, nodes, queues, seconds, iters, status)
-
-
 class BFS(Agent):
     """
     Breadth-first search (reference agents.py:92-131) with whole levels expanded on the GPU; solution,
@@ -243,7 +140,7 @@ class BFS(Agent):
         time_limit, max_states = self.reset(time_limit, max_states)
         self.tt.tick()
         dev = self._device_for(max_states)
-        deadline = (lambda: self.tt.tock() >= time_limit) if time_limit < 1e10 else None
+        deadline = None if _unbounded(time_limit) else (lambda: self.tt.tock() >= time_limit)
         solved, actions, seen = dev.search(np.asarray(state), int(min(max_states, dev.max_states)), deadline)
         self._explored_states = seen
         self.action_queue = deque(actions)
@@ -266,7 +163,7 @@ class BFS(Agent):
             if solved[g]:
                 lengths[g] = len(self.action_queue)
         status = np.where(solved, np.where(nodes == 0, 4, 1), 2)
-        return BatchResult(solved, lengths, nodes, queues, tt.tock(), levels, status, each)
+        return BatchResult(solved, lengths, nodes, QueueTable.from_queues(queues), tt.tock(), levels, status, each)
 
     def __str__(self):
         return "Breadth-first search"
@@ -371,7 +268,6 @@ class MCTS(DeepAgent):
 
     nu = 100
     snapshot_trees = None      # test hook: a dict -> {game: tree_arrays()} of every tree as its search left it (before graph completion)
-    refill_level_budget = 0    # new levels per descent and iteration while scrambles wait for a slot (0 = no limit)
 
     def __init__(self, net, c: float, search_graph: bool, net_dtype=F32_SPLIT, use_graph: bool = True,
                  max_path: int = None, sync_every: int = 16, level_budget="auto", deterministic: bool = False):
@@ -395,16 +291,10 @@ class MCTS(DeepAgent):
         budget of 32 gains 4 % (23.9 vs 22.9 M nodes/s), but a run to completion gets 2.5x SLOWER (6.1 s vs
         2.4 s: the last stragglers are suspended over and over), so "auto" means 0 (strict lock step).
         """
-        super().__init__(net)
+        super().__init__(net, net_dtype, deterministic)
         self.level_budget = level_budget
         self.c, self.search_graph = float(c), bool(search_graph)
-        if deterministic:
-            if net_dtype not in (F32_SPLIT, F32_SPLIT_DET):
-                raise ValueError("deterministic=True runs on the split engine (net_dtype=F32_SPLIT): the library GEMMs of the other engines "
-                                 "choose their kernels by batch shape")
-            net_dtype = F32_SPLIT_DET
-        self.deterministic = net_dtype == F32_SPLIT_DET
-        self.net_dtype, self.use_graph, self.max_path, self.sync_every = net_dtype, use_graph, max_path, sync_every
+        self.use_graph, self.max_path, self.sync_every = use_graph, max_path, sync_every
         self.forest = None
         self._last_forest = None   # the forest the last search ended in (a compacted one after `compact`)
         self._tree = None      # host copy of game 0's tree, for the reference's inspectable attributes
@@ -416,9 +306,6 @@ class MCTS(DeepAgent):
 
     def __str__(self):
         return ("BFS" if self.search_graph else "Naive") + f" MCTS (c={self.c})"
-
-    def __len__(self):
-        return self._explored_states
 
     # ---- batched search --------------------------------------------------------------------------
     def _forest_for(self, n_trees: int, capacity: int) -> md.MCTSForest:
@@ -456,7 +343,7 @@ class MCTS(DeepAgent):
         itself starts at full speed: allocates the forest (HBM, zero-filled), builds the inference engine and captures the HIP
         graph of every launch size the forest will be narrowed to (~0.1 s per size for the split engine: the allocations of
         its activations).  Optional: a search on an unprepared agent does the same work on the way."""
-        cap_states = int(max_states) if max_states and max_states < int(1e10) else time_only_capacity(n_trees)
+        cap_states = int(max_states) if max_states and not _unbounded(max_states) else time_only_capacity(n_trees)
         forest = self._forest_for(int(n_trees), max(cap_states, 16))
         if self.use_graph:
             forest.capture_all(self.c, cap_states)
@@ -492,8 +379,7 @@ class MCTS(DeepAgent):
     def start_batch(self, states, time_limit: float = None, max_states: int = None, compact: bool = True,
                     slots: int = None, one_launch: bool = True) -> "MCTSRun":
         time_limit, max_states = self.reset(time_limit, max_states)
-        roots = states if isinstance(states, DeviceCubes) else DeviceCubes.from_numpy(np.asarray(states))
-        return MCTSRun(self, roots, time_limit, max_states, compact, slots, one_launch)
+        return MCTSRun(self, DeviceCubes.of(states), time_limit, max_states, compact, slots, one_launch)
 
     # ---- the reference's single-state API ----------------------------------------------------------
     def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
@@ -530,7 +416,52 @@ def _to_device_async(arr: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr)).pin_memory().to(device, non_blocking=True)
 
 
-class MCTSRun:
+class SlotPool:
+    """
+    Continuous batching on the host: `n_games` games go, in order, through the S slots of a device batch.  `owner[s]` is the game in
+    slot s (-1: its result is taken and nobody moved in), `next_game` the first game still waiting.  A game's wall interval
+    (`BatchResult.game_seconds`) runs on `clock` (the agent's `tt.tock`) from the plant of its root to the host's first sighting of it
+    finished, or to the end of the search.
+    """
+
+    def __init__(self, n_games: int, slots, clock):
+        self.n_games, self.clock = n_games, clock
+        self.S = n_games if slots is None else max(1, min(int(slots), n_games))
+        self.owner = np.arange(self.S)              # the first S games start in the slots; the others move in as games finish
+        self.next_game = self.S
+        self._t_start = np.zeros(n_games)           # per game: when its root was planted ...
+        self._t_end = np.full(n_games, np.nan)      # ... and when the host first saw it finished (NaN: not yet)
+
+    @property
+    def waiting(self) -> bool:
+        return self.next_game < self.n_games
+
+    def sighted(self, done: np.ndarray, now: float):
+        """The host has just seen the games in slots `done` finished: the first sighting of a game counts."""
+        g = self.owner[done]
+        self._t_end[g[np.isnan(self._t_end[g])]] = now
+
+    def refill(self, done: np.ndarray, plant) -> np.ndarray:
+        """Slots `done` (results taken) go to the games still waiting, if any: `plant(slots, first)` queues the roots of games first,
+        first + 1, ... into `slots`; their intervals begin when it returns.  -> the slots that got a game (the others stay empty)."""
+        first, k = self.next_game, min(len(done), self.n_games - self.next_game)
+        plant(done[:k], first)
+        self.owner[done] = -1
+        self.owner[done[:k]] = np.arange(first, first + k)
+        self._t_start[first:first + k] = self.clock()
+        self.next_game += k
+        return done[:k]
+
+    def close(self, result: BatchResult, seconds: float, exhausted_status: int):
+        """The search ended after `seconds`: games that never got a slot end there, unsolved and with nothing explored, and so do the
+        intervals of the games still running; -> `result.game_seconds`."""
+        if self.waiting:
+            result.status[self.next_game:] = exhausted_status
+            self._t_start[self.next_game:] = seconds
+        result.game_seconds = np.where(np.isnan(self._t_end), seconds, self._t_end) - self._t_start
+
+
+class MCTSRun(SlotPool):
     """
     A batched MCTS search in progress: `round()` queues the next lock-step iterations, `finish()` returns the
     per-game BatchResult.  All trees of the forest advance together, `sync_every` iterations per round; the host
@@ -542,17 +473,15 @@ class MCTSRun:
     with everybody else.  Once nobody is waiting the finished trees stay where they are: they are post-processed in place
     (`_Harvest(trees=...)`) and dropped from the iteration launches by a shorter list of trees (`MCTSForest.set_active`),
     so narrowing a forest costs nothing, whatever the per-tree capacity (copying the survivors of 1 024 trees of capacity
-    175 000, the reference's default max_states, took 0.55 s per halving).  While games are waiting, descents may be cut
-    at the agent's `refill_level_budget` new levels per iteration (0 = off, the default since descents follow lines: a
-    budget then costs more iterations than it saves time per iteration).
+    175 000, the reference's default max_states, took 0.55 s per halving).
     """
 
     def __init__(self, agent: "MCTS", roots: DeviceCubes, time_limit: float, max_states: int, compact: bool, slots, one_launch: bool = True):
+        super().__init__(roots.n, slots, agent.tt.tock)
         self.agent, self.roots, self.time_limit, self.compact = agent, roots, time_limit, compact
         self.max_states, self.slots, self.one_launch = max_states, slots, one_launch
-        self.n_games = roots.n
-        S = self.S = self.n_games if slots is None else max(1, min(int(slots), self.n_games))
-        self.cap_states = int(max_states) if max_states < int(1e10) else time_only_capacity(S)
+        S = self.S
+        self.cap_states = time_only_capacity(S) if _unbounded(max_states) else int(max_states)
         forest = self.forest = agent._forest_for(S, max(self.cap_states, 16))
         forest._run = weakref.ref(self)     # who steps this forest: an agent does not hand its memory on under a run that is not done
         agent.tt.tick()
@@ -562,14 +491,7 @@ class MCTSRun:
         # iterations that may be queued before the host has looked at the node counts: what a planted tree's first rows cover
         # (16 384 rows: its first ~1 360 iterations), so that a long `sync_every` cannot make trees sit out behind the kernel's guard
         forest._steps_covered = min(2 * agent.sync_every, max(1, (forest._first_rows() - 14) // 12))
-        self.t_start = np.zeros(self.n_games)               # per game: seconds on the agent's clock when its tree was planted ...
-        self.t_end = np.full(self.n_games, np.nan)          # ... and when the host first saw it finished (NaN: still running)
-        self.owner = np.arange(S)          # game index of every slot; -1 once its result has been taken and nobody moved in
         self.stale_until = np.full(S, -1)  # snapshots up to this index predate the tree that now lives in the slot
-        self.next_game = S
-        self.base_budget = forest.level_budget
-        if self.next_game < self.n_games and agent.level_budget == "auto":
-            forest.level_budget = agent.refill_level_budget
         self.min_refill = max(8, S // 32)
         self.stats = agent.refill_stats = {"iterations": 0, "harvests": 0, "refills": 0, "compactions": 0,
                                            "host_enqueue_s": 0.0, "host_wait_s": 0.0, "host_process_s": 0.0}
@@ -588,6 +510,16 @@ class MCTSRun:
                 self.parts.append((h.games, h.result()))
                 self.harvests.remove(h)
 
+    def _extract(self, forest: md.MCTSForest, games: np.ndarray, **which) -> _Harvest:
+        """Result extraction of trees of `forest` (`which`: see `_Harvest`) on the side stream, behind all that this stream has queued."""
+        ev = torch.cuda.Event()
+        ev.record()
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ev)
+            h = _Harvest(self.agent, forest, games, **which)
+        self.harvests.append(h)
+        return h
+
     GRAVE = 256   # finished trees collected before their graph completion / BFS shortening is launched
 
     def _flush_grave(self):
@@ -599,12 +531,7 @@ class MCTSRun:
         g, n = self.grave, self.grave_fill
         self.stats["flushes"] = self.stats.get("flushes", 0) + 1
         g.status[n:] = md.RUNNING          # slots beyond the fill are not trees
-        ev = torch.cuda.Event()
-        ev.record()
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(ev)
-            h = _Harvest(self.agent, g, self.grave_games[:n].copy(), n=n, trees_host=np.arange(n))
-        self.harvests.append(h)
+        h = self._extract(g, self.grave_games[:n].copy(), n=n, trees_host=np.arange(n))
         self.grave_event, self.grave_fill = h.event, 0
 
     def _flush_resting(self):
@@ -617,11 +544,7 @@ class MCTSRun:
         trees = _to_device_async(idx_np.astype(np.int32), forest.status.device)
         games = self.games_of_resting[idx_np].copy()
         self.stats["flushes"] = self.stats.get("flushes", 0) + 1
-        ev = torch.cuda.Event()
-        ev.record()
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(ev)
-            self.harvests.append(_Harvest(self.agent, forest, games, trees=trees, trees_host=idx_np))
+        self._extract(forest, games, trees=trees, trees_host=idx_np)
 
     def _snapshot(self, idx_np: np.ndarray):
         if self.agent.snapshot_trees is not None:
@@ -644,34 +567,24 @@ class MCTSRun:
         """Copies the finished trees `idx_np` out of the forest (their slots are needed or dropped): what result extraction
         reads of them goes into the results forest, which is processed GRAVE trees at a time on the side stream."""
         forest, agent = self.forest, self.agent
+        self.stats["harvests"] += 1
         self._snapshot(idx_np)
         games = self.owner[idx_np].copy()
         if agent._tree_src is None and (games == 0).any():
             # game 0's tree stays inspectable (the reference's attributes): a search forest of its own, with this one tree
             first = idx_np[games == 0][:1]
             one = forest.subset(first, results_only=False)
-            ev = torch.cuda.Event()
-            ev.record()
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ev)
-                self.harvests.append(_Harvest(agent, one, np.zeros(1, dtype=np.int64)))
+            self._extract(one, np.zeros(1, dtype=np.int64))
             agent._tree_src = (one, 0)
             idx_np, games = idx_np[games != 0], games[games != 0]
             if len(idx_np) == 0:
-                self.stats["harvests"] += 1
                 return
         # a last path beyond the first block, or (searches bounded by time alone) more nodes than the grave's rows: a results forest of its own
         deep = (forest.paths_seen[idx_np] > forest.path_block) | (forest.nodes_seen[idx_np] + 13 > min(forest.C, forest.COPY_CAPACITY_MAX))
         if deep.any():
-            sub = forest.subset(idx_np[deep], results_only=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ev)
-                self.harvests.append(_Harvest(agent, sub, games[deep]))
+            self._extract(forest.subset(idx_np[deep], results_only=True), games[deep])
             idx_np, games = idx_np[~deep], games[~deep]
             if len(idx_np) == 0:
-                self.stats["harvests"] += 1
                 return
         if len(idx_np) < self.GRAVE // 2:
             if self.grave is None:
@@ -686,15 +599,8 @@ class MCTSRun:
             self.grave.bury(self.grave_fill, forest, idx_np)
             self.grave_games[self.grave_fill:self.grave_fill + len(idx_np)] = games
             self.grave_fill += len(idx_np)
-            self.stats["harvests"] += 1
             return
-        sub = forest.subset(idx_np, results_only=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(ev)
-            self.harvests.append(_Harvest(agent, sub, games))
-        self.stats["harvests"] += 1
+        self._extract(forest.subset(idx_np, results_only=True), games)
 
     def round(self, max_steps: int = None):
         """Queues up to `sync_every` iterations, then acts on the tree states of the round before."""
@@ -736,7 +642,7 @@ class MCTSRun:
                     if not getattr(self, "_hbm_warned", False):
                         warnings.warn(f"MCTS: no more HBM behind the trees' node rows ({e}); the trees that need more stop growing", RuntimeWarning)
                         self._hbm_warned = True
-                    if self.time_limit >= 1e10:
+                    if _unbounded(self.time_limit):
                         self.done = True
                         return
                 forest._steps_covered = 2 * agent.sync_every
@@ -756,30 +662,21 @@ class MCTSRun:
         fresh = self.stale_until < qi
         running = live & ((status == md.RUNNING) | ~fresh)      # a slot refilled after the snapshot runs by definition
         done = np.flatnonzero(live & fresh & (status != md.RUNNING))
-        if len(done):                                           # the host has just seen these games finished (first sighting counts)
-            g = owner[done]
-            first = np.isnan(self.t_end[g])
-            self.t_end[g[first]] = agent.tt.tock()
+        self.sighted(done, agent.tt.tock())
         n_run = int(running.sum())
         out_of_time = agent.tt.tock() >= self.time_limit
-        waiting = self.next_game < self.n_games
+        waiting = self.waiting
         self._drain(False)
         if out_of_time or (n_run == 0 and not waiting):
             self.done = True
             return
         if waiting and len(done) and (len(done) >= self.min_refill or n_run == 0):
             self._harvest(done)
-            k = min(len(done), self.n_games - self.next_game)
-            idx = _to_device_async(done[:k].astype(np.int32), forest.status.device)
-            forest.plant(idx, self.roots, self.next_game, self.plant_states, slots_host=done[:k])   # the waiting scrambles move in: roots evaluated by the next two iterations
-            owner[done] = -1
-            owner[done[:k]] = np.arange(self.next_game, self.next_game + k)
-            self.t_start[self.next_game:self.next_game + k] = agent.tt.tock()
-            self.stale_until[done[:k]] = self.q - 1     # every snapshot queued so far predates the adoption
-            self.next_game += k
+            def plant(slots, first):   # the waiting scrambles move in: roots evaluated by the next two iterations
+                idx = _to_device_async(slots.astype(np.int32), forest.status.device)
+                forest.plant(idx, self.roots, first, self.plant_states, slots_host=slots)
+            self.stale_until[self.refill(done, plant)] = self.q - 1     # every snapshot queued so far predates the adoption
             self.stats["refills"] += 1
-            if self.next_game >= self.n_games:
-                forest.level_budget = self.base_budget   # nobody is waiting any more: strict lock step for the tail
         elif not waiting and self.compact and forest.rung_for(n_run) < forest.G:
             # fewer running trees than the next smaller launch size: the finished ones rest where they are, the iterations
             # go on with a shorter list of trees (nothing is copied)
@@ -847,10 +744,7 @@ class MCTSRun:
         self._flush_grave()
         self._drain(True)
         result = BatchResult.merge(self.n_games, self.parts, seconds)
-        if self.next_game < self.n_games:   # games that never got a slot before the time limit: unsolved, nothing explored
-            result.status[self.next_game:] = md.EXHAUSTED
-            self.t_start[self.next_game:] = seconds
-        result.game_seconds = np.where(np.isnan(self.t_end), seconds, self.t_end) - self.t_start   # (still running at the end: until the end)
+        self.close(result, seconds, md.EXHAUSTED)
         self.done = True
         if agent._overflowed(forest.engine):   # the split engine could not represent an activation: the same search in fp32
             again = MCTSRun(agent, self.roots, self.time_limit, self.max_states, self.compact, self.slots, self.one_launch)
@@ -873,12 +767,8 @@ class AStar(DeepAgent):
     def __init__(self, net, lambda_: float, expansions: int, net_dtype=F32_SPLIT, deterministic: bool = False):
         """deterministic: as for `MCTS` -- one layer plan of the split engine for every row count, so a problem's search does not depend
         on which other problems share its batch."""
-        super().__init__(net)
-        if deterministic:
-            if net_dtype not in (F32_SPLIT, F32_SPLIT_DET):
-                raise ValueError("deterministic=True runs on the split engine (net_dtype=F32_SPLIT)")
-            net_dtype = F32_SPLIT_DET
-        self.lambda_, self.expansions, self.net_dtype = float(lambda_), int(expansions), net_dtype
+        super().__init__(net, net_dtype, deterministic)
+        self.lambda_, self.expansions = float(lambda_), int(expansions)
         self.batch = None
         self._arrays = None
 
@@ -888,9 +778,6 @@ class AStar(DeepAgent):
 
     def __str__(self):
         return f"AStar (lambda={self.lambda_}, N={self.expansions})"
-
-    def __len__(self):
-        return self._explored_states
 
     def _batch_for(self, n_problems: int, capacity: int):
         b = self.batch
@@ -916,20 +803,24 @@ class AStar(DeepAgent):
         nodes, status EXHAUSTED and 0 seconds.
         """
         time_limit, max_states = self.reset(time_limit, max_states)
-        roots = states if isinstance(states, DeviceCubes) else DeviceCubes.from_numpy(np.asarray(states))
-        n_games = roots.n
-        S = n_games if slots is None else max(1, min(int(slots), n_games))
-        if max_iterations is not None and S < n_games:
+        return self._search(DeviceCubes.of(states), time_limit, max_states, max_iterations, slots)
+
+    def _search(self, roots: DeviceCubes, time_limit: float, max_states: int, max_iterations, slots) -> BatchResult:
+        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given)."""
+        pool = SlotPool(roots.n, slots, self.tt.tock)
+        S, owner = pool.S, pool.owner
+        if max_iterations is not None and pool.waiting:
             raise ValueError("max_iterations applies to plain batches only (slots >= number of games)")
-        cap_states = int(max_states) if max_states < int(1e10) else astar_time_only_capacity(S)
+        cap_states = astar_time_only_capacity(S) if _unbounded(max_states) else int(max_states)
         batch = self._batch_for(S, max(cap_states, 12 * self.expansions + 1))
         self._arrays = None
         self.tt.tick()
         batch.reset(roots)                          # the first S scrambles; the others move in as problems finish
-        owner = np.arange(S)                        # game of every slot; -1 once its result is taken and nobody moved in
         planted_at = np.zeros(S, dtype=np.int64)    # loop iteration at which the slot's problem was planted
-        t_start, t_end = np.zeros(n_games), np.full(n_games, np.nan)
-        next_game, it, taken = S, 0, []             # taken: (games, pinned copies, event) of extracted slots
+        it, taken = 0, []                           # taken: (games, pinned copies, event) of extracted slots
+
+        def plant(into, first):
+            batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first)
         while max_iterations is None or it < max_iterations:
             batch.iteration(self.lambda_, cap_states)
             it += 1
@@ -937,30 +828,21 @@ class AStar(DeepAgent):
             now = self.tt.tock()
             live = owner >= 0
             ended = live & (status != ad.RUNNING)
-            g = owner[ended]
-            t_end[g[np.isnan(t_end[g])]] = now      # first sighting of a finished problem
-            waiting = next_game < n_games
-            if now >= time_limit or not (live & ~ended).any() and not waiting:
-                break
             done = np.flatnonzero(ended)
-            if waiting and len(done):
+            pool.sighted(done, now)
+            if now >= time_limit or not (live & ~ended).any() and not pool.waiting:
+                break
+            if pool.waiting and len(done):
                 # a queue is no longer than its problem's G at the goal, and G <= the iterations since the plant (G[parent] + 1,
                 # relaxations only lower it, children are appended one iteration after their parent): this width always fits
                 width = int(max(1, (it - planted_at[done]).max()))
                 taken.append(self._take(batch, done, owner[done].copy(), width))
                 if 0 in owner[done]:
                     self._arrays = batch.problem_arrays(int(np.flatnonzero(owner == 0)[0]))   # game 0 stays inspectable
-                k = min(len(done), n_games - next_game)
-                batch.plant(_to_device_async(done[:k].astype(np.int32), batch.device), roots, next_game)
-                owner[done] = -1
-                owner[done[:k]] = np.arange(next_game, next_game + k)
-                planted_at[done[:k]] = it
-                t_start[next_game:next_game + k] = self.tt.tock()
-                next_game += k
+                planted_at[pool.refill(done, plant)] = it
         torch.cuda.synchronize()
         if self._overflowed(batch.engine):   # the split engine could not represent an activation: the same search in fp32
-            return self.search_batch(roots, time_limit if time_limit < 1e10 else None, max_states if max_states < int(1e10) else None,
-                                     max_iterations, slots)
+            return self._search(roots, time_limit, max_states, max_iterations, slots)
         seconds = self.tt.tock()
         left = np.flatnonzero(owner >= 0)
         parts = [self._result(*t) for t in taken]
@@ -969,11 +851,8 @@ class AStar(DeepAgent):
                                     for x in (batch.status, batch.n_nodes, batch.iterations))
             lens, queues = batch.solutions(left)
             parts.append((owner[left], self._part(status, nodes, iters, lens, queues)))
-        result = BatchResult.merge(n_games, parts, seconds)
-        if next_game < n_games:   # games that never got a slot before the time limit: unsolved, nothing explored
-            result.status[next_game:] = ad.EXHAUSTED
-            t_start[next_game:] = seconds
-        result.game_seconds = np.where(np.isnan(t_end), seconds, t_end) - t_start   # (still running at the end: until the end)
+        result = BatchResult.merge(pool.n_games, parts, seconds)
+        pool.close(result, seconds, ad.EXHAUSTED)
         self._explored_states = int(result.nodes[0])
         self.action_queue = result.queues[0]
         return result
@@ -1072,10 +951,10 @@ class _StepAgent(Agent):
     @no_grad
     def search_batch(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
         time_limit, max_states = self.reset(time_limit, max_states)
-        cubes = states if isinstance(states, DeviceCubes) else DeviceCubes.from_numpy(np.asarray(states))
+        cubes = DeviceCubes.of(states)
         cubes = DeviceCubes(cubes.soa.clone(), cubes.n)
         B = cubes.n
-        cap = int(max_states) if max_states < int(1e10) else DEFAULT_STEP_CAP
+        cap = DEFAULT_STEP_CAP if _unbounded(max_states) else int(max_states)
         self.tt.tick()
         solved = cubes.is_solved().clone()
         root_solved = solved.clone()
@@ -1105,7 +984,8 @@ class _StepAgent(Agent):
         # every step, so the look behind step i sees it done); games that ran to the end: the batch's seconds
         after = np.array(stamps[1:] + [seconds]) if stamps else np.zeros(0)
         each = np.where(steps > 0, after[np.maximum(steps, 1) - 1] if len(after) else seconds, stamps[0] if stamps else seconds)
-        return BatchResult(solved_h, lengths, steps.astype(np.int64), queues, seconds, steps, status, np.asarray(each, dtype=np.float64))
+        each = np.asarray(each, dtype=np.float64)
+        return BatchResult(solved_h, lengths, steps.astype(np.int64), QueueTable.from_queues(queues), seconds, steps, status, each)
 
     def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
         return bool(self.search_batch(np.asarray(state)[None], time_limit, max_states).solved[0])
@@ -1131,8 +1011,8 @@ class RandomSearch(_StepAgent):
 
 class _DeepStepAgent(_StepAgent, DeepAgent):
     def __init__(self, net, net_dtype=F32_SPLIT):
-        DeepAgent.__init__(self, net)
-        self.net_dtype, self._engine = net_dtype, None
+        DeepAgent.__init__(self, net, net_dtype)
+        self._engine = None
 
     def reset(self, time_limit, max_states):
         from librubiks.model import make_inference_net
@@ -1195,8 +1075,8 @@ class EGVM(DeepAgent):
     """
 
     def __init__(self, net, epsilon: float, workers: int, depth: int, net_dtype=F32_SPLIT):
-        super().__init__(net)
-        self.epsilon, self.workers, self.depth, self.net_dtype = epsilon, workers, depth, net_dtype
+        super().__init__(net, net_dtype)
+        self.epsilon, self.workers, self.depth = epsilon, workers, depth
 
     @classmethod
     def from_saved(cls, loc: str, use_best: bool, epsilon: float, workers: int, depth: int, **kw):
@@ -1265,5 +1145,5 @@ class EGVM(DeepAgent):
             solved.append(ok), lengths.append(len(self.action_queue) if ok else -1)
             nodes.append(len(self)), queues.append(self.action_queue)
         solved = np.array(solved)
-        return BatchResult(solved, np.array(lengths), np.array(nodes, dtype=np.int64), queues, tt.tock(),
+        return BatchResult(solved, np.array(lengths), np.array(nodes, dtype=np.int64), QueueTable.from_queues(queues), tt.tock(),
                            np.zeros(len(states), dtype=int), np.where(solved, 1, 2))

@@ -18,6 +18,7 @@ from librubiks import _hip
 from librubiks.cube.device import DeviceCubes
 from librubiks.model import make_inference_net, net_fingerprint
 from librubiks.solving.mcts_device import unpack_keys
+from librubiks.solving.results import QueueTable
 
 RUNNING, SOLVED, EXHAUSTED, OPEN_EMPTY, ROOT_SOLVED = 0, 1, 2, 3, 4
 PATH_UNSOLVED, PATH_CORRUPT, PATH_NO_PROBLEM = -1, -2, -3    # rc_astar_solutions' negative lengths
@@ -127,7 +128,6 @@ class AStarBatch:
         """(int64 lengths, QueueTable) of `problems` (sequence of problem indices): the queues walked on the device
         (rc_astar_solutions); a queue longer than `width` is read again with a table as wide as the longest.  Length -1 =
         unsolved (empty queue).  Raises if a walk met indices that are not the problem's (synchronises)."""
-        from librubiks.solving.agents import QueueTable
         idx = torch.as_tensor(np.asarray(problems, dtype=np.int32), device=self.device)
         table, lengths = self.solutions_launch(idx, width)
         lens = lengths.cpu().numpy().astype(np.int64)

@@ -945,11 +945,3 @@ class MCTSForest:
                 kind, base, off = f"? ({e})", 0, 0
             out.append(f"{name} @0x{addr:x}: {kind}" + (f" (range 0x{base:x} + {off})" if base else ""))
         return "; ".join(out)
-
-    def neighbors_of(self, t: int, n: int) -> np.ndarray:
-        lo = t * (self.C + 1)
-        return self.nbr[lo:lo + n + 1].cpu().numpy().astype(np.int64)
-
-    def paths(self):
-        """(path_len[B], path_act[B, path_block]) on the host: the paths' first block (`read_path` for a deeper one)."""
-        return self.path_len.cpu().numpy(), self.path_act[0].cpu().numpy()

@@ -117,6 +117,49 @@ def test_queue_table_padded_matches_the_per_game_deques():
     assert empty.shape == (2, 0) and list(lens) == [0, 0]
 
 
+def test_slot_pool_owners_and_game_intervals():
+    """SlotPool, the host bookkeeping of continuous batching that MCTSRun and AStar.search_batch share: a scripted sequence of sightings
+    and refills on a scripted clock.  A game's interval runs from the clock's reading once its root has been planted (0 for the first S
+    games) to its FIRST sighting as finished; a game still running at the end runs until the end; a game that never got a slot is
+    EXHAUSTED with an empty interval; `from_queues` tables behave like the list they were built from."""
+    import numpy as np
+    from librubiks.solving.agents import BatchResult, QueueTable, SlotPool
+    clock, planted = iter([2.5, 4.5]), []
+
+    def plant(slots, first):
+        planted.append((list(slots), first))
+
+    pool = SlotPool(6, 3, lambda: next(clock))
+    assert (pool.n_games, pool.S, pool.next_game, pool.waiting) == (6, 3, 3, True) and list(pool.owner) == [0, 1, 2]
+    pool.sighted(np.array([1]), 1.0)
+    pool.sighted(np.array([1, 2]), 2.0)                     # game 1 was seen before: its end stays 1.0
+    assert list(pool.refill(np.array([1, 2]), plant)) == [1, 2]
+    assert list(pool.owner) == [0, 3, 4] and pool.next_game == 5 and pool.waiting
+    pool.sighted(np.array([0, 2]), 4.0)
+    assert list(pool.refill(np.array([0, 2]), plant)) == [0]   # one game was waiting: the other slot stays empty
+    assert list(pool.owner) == [5, 3, -1] and pool.next_game == 6 and not pool.waiting
+    assert planted == [([1, 2], 3), ([0], 5)]
+    pool.sighted(np.array([0]), 6.0)
+    result = BatchResult(None, None, None, None, 7.0, None, np.ones(6, dtype=np.int64))
+    pool.close(result, 7.0, 2)
+    #                                  game 0      1          2          3 (running) 4          5
+    assert np.array_equal(result.game_seconds, [4.0 - 0.0, 1.0 - 0.0, 2.0 - 0.0, 7.0 - 2.5, 4.0 - 2.5, 6.0 - 4.5])
+    assert list(result.status) == [1] * 6
+
+    late = SlotPool(5, 2, lambda: 0.0)                      # the time limit ends the search before games 2, 3, 4 got a slot
+    late.sighted(np.array([0]), 0.5)
+    result = BatchResult(None, None, None, None, 3.0, None, np.ones(5, dtype=np.int64))
+    late.close(result, 3.0, 2)
+    assert list(result.status) == [1, 1, 2, 2, 2] and np.array_equal(result.game_seconds, [0.5, 3.0, 0.0, 0.0, 0.0])
+    assert SlotPool(4, None, None).S == 4 and SlotPool(4, 9, None).S == 4 and SlotPool(4, 0, None).S == 1
+
+    from collections import deque
+    queues = [deque([3, 1, 4]), deque(), deque([11])]
+    table = QueueTable.from_queues(queues)
+    assert len(table) == 3 and [table[g] for g in range(3)] == queues and isinstance(table[0], deque)
+    assert list(table.lengths()) == [3, 0, 1]
+
+
 def test_vmm_classify_replays_an_event_log(tmp_path):
     """tools/vmm_classify.py on a hand-written event file (the format rubiks_vmm.hip writes under RUBIKS_VMM_LOG): a live range with
     two mapped chunks, its alignment slack, a released range on the idle list, a reused one, and addresses that were never ours."""
