@@ -349,6 +349,12 @@ class Train:
 
     @staticmethod
     def _get_batches(size: int, bsize: int):
-        """Contiguous slices; the reference shuffles an index array it then never uses (train.py:400-410)."""
+        """Contiguous slices.  The reference shuffles an index array and then slices without it (train.py:400-410):
+        the order of the states is unaffected, but the shuffle's draws move the global np.random stream, and every later
+        scramble -- of the next rollouts and of the evaluations in between -- depends on where that stream stands.  The draws
+        are kept, by the same call, so that equal seeds give the reference's scrambles in every rollout
+        (tests/test_train_parity_gpu.py).  Data-parallel: called outside `_rank_stream`, with the same size on every rank,
+        so the common stream stays common."""
+        np.random.shuffle(np.arange(size))
         n = int(np.ceil(size / bsize))
         return [slice(b * bsize, min(size, (b + 1) * bsize)) for b in range(n)]

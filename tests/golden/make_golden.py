@@ -6,7 +6,8 @@ Run only in the build container, where the reference is mounted read-only:
     cd /tmp && PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg PYTHONPATH=/root/reference \
         python /root/repo/tests/golden/make_golden.py [cube] [bfs] [bfs_cut] [agents] [adi] [simple] [model]
 
-`solve` (make_golden_solve.py, trained-weight MCTS / A* outcomes) runs only when named, like `model`.
+`solve` (make_golden_solve.py, trained-weight MCTS / A* outcomes) and `train` (make_golden_train.py, the training loop
+rollout by rollout) run only when named, like `model`.
 
 The fixtures are DATA (inputs + the reference's outputs).  No reference source travels with them.
 The GPU box never runs this script (it has no /root/reference); it only reads the committed files.
@@ -230,3 +231,6 @@ if __name__ == "__main__":
     if "solve" in what:
         from make_golden_solve import make_solve
         make_solve()
+    if "train" in what:
+        from make_golden_train import make_train
+        make_train()
