@@ -588,6 +588,79 @@ int rc_astar_plant(const rc_astar_t *a, const int32_t *slots, uint32_t n, const 
 int rc_astar_solutions(const rc_astar_t *a, const int32_t *problems, uint32_t n, uint8_t *queues, uint32_t width,
                        int32_t *lengths, rc_stream_t stream);
 
+/* ---- batched EGVM: S games of W epsilon-greedy rollouts each, all advanced in lock step ------------
+ *
+ * Replaces the per-game Python loop of librubiks/solving/agents.py:649-726 (class EGVM).  A round of every running game =
+ *     for d in 0 .. D - 1:  [network on the S W rows of rows_soa: 12 logits + value per row] -> rc_egvm_step(d)
+ *     [network on the rows once more: the values of the last depth] -> rc_egvm_round_end
+ * Row g W + w of rows_soa is worker w of the game in slot g.  The random decisions of a round are the host's (one byte per row
+ * and depth, drawn from the game's own np.random stream in the reference's order, agents.py:694-698): they do not depend on the
+ * device, so a round runs without the host.  The value of the state a worker reaches at depth d arrives with the forward pass
+ * of step d + 1, so no W x D array of visited states is kept (agents.py:681-682): every row keeps a running best of (value,
+ * depth, state), replaced on a strictly greater value, and the round ends on the best row of lowest index -- np.argmax over
+ * the reference's worker-major index w D + d (agents.py:674-676), a NaN counting as the maximum.
+ * Device pointers; nothing needs initialising except through rc_egvm_plant.
+ */
+#define RC_EGVM_RUNNING 0
+#define RC_EGVM_SOLVED 1        /* a worker reached the solved cube (agents.py:710-713) */
+#define RC_EGVM_EXHAUSTED 2     /* nodes + W D > max_states (agents.py:665) */
+#define RC_EGVM_QUEUE_FULL 3    /* the round's path prefix does not fit the queue row: nothing was written for that round */
+#define RC_EGVM_ROOT_SOLVED 4   /* agents.py:661 */
+#define RC_EGVM_NO_HIT 0xffffffffu
+#define RC_EGVM_POLICY 255      /* decision byte: the first maximum of the row's 12 logits; 0 .. 11: that action */
+
+typedef struct rc_egvm {
+    uint32_t n_slots;     /* S: games searched at a time */
+    uint32_t workers;     /* W (agents.py:651), 1 .. 65 535 */
+    uint32_t depth;       /* D (agents.py:652), 1 .. 32 768 */
+    uint32_t queue_width; /* bytes per row of `queues` */
+    size_t stride;        /* bytes between the planes of rows_soa and of best_soa: multiple of 16, >= round_up(S W, 16) */
+    int8_t *rows_soa;     /* [20][stride] the workers' current states = the network's input */
+    int8_t *best_soa;     /* [20][stride] per row: the visited state of highest value so far in this round */
+    float *best_value;    /* [S W] its value ... */
+    int32_t *best_depth;  /* [S W] ... and depth (-1: none yet) */
+    uint8_t *paths;       /* [S][W][D] actions taken in this round (agents.py:680) */
+    uint32_t *hit;        /* [S] (d << 16 | w) of the round's first solved worker: first depth, then lowest worker; RC_EGVM_NO_HIT */
+    int8_t *current;      /* [S][20] the state the game's next round starts from (agents.py:676) */
+    uint8_t *queues;      /* [S][queue_width] action queues (agents.py:677,712) */
+    int64_t *status;      /* [S] RC_EGVM_* */
+    int64_t *nodes;       /* [S] len(agent) (agents.py:672,711) */
+    int64_t *queue_len;   /* [S] */
+    int64_t *rounds;      /* [S] rounds completed since the plant */
+} rc_egvm_t;
+
+/* Depth step d of the round (agents.py:690-716) for all S W rows in one launch: with d > 0 the value column of `head` is the
+ * value of the row's current state and updates its running best; the action is decisions_row[row] (0 .. 11) or, for
+ * RC_EGVM_POLICY, the first maximum of the row's 12 logits as np.argmax finds it (a NaN is the maximum); the cube is turned,
+ * paths[g][w][d] written, and a solved row claims its game's hit word with atomicMin.  Rows of games that are not running, or
+ * whose hit word names an earlier depth, are not touched.  `head` is [S W][ld] with 12 logits then the value per row, float or
+ * bf16 (head_is_bf16), ld >= 13: what rc_mcts_step_head reads.  decisions_row: S W bytes. */
+int rc_egvm_step(const rc_egvm_t *e, uint32_t d, const uint8_t *decisions_row, const void *head, size_t ld, int head_is_bf16,
+                 rc_stream_t stream);
+/* End of the round for every running game (agents.py:666-677,710-713).  With a hit (d, w): nodes += (d + 1) W, the queue gets
+ * paths[w][0 .. d], status RC_EGVM_SOLVED.  Without: values_last[row] (float [S W]) is the value of the row's state after the
+ * last depth and is folded into the running bests, the best row of lowest index (w*, d*) is found, nodes += W D, the queue
+ * gets paths[w*][0 .. d*], every worker of the game restarts from that state, and the game is RC_EGVM_EXHAUSTED if
+ * nodes + W D > max_states.  A prefix that does not fit the queue row is not written: RC_EGVM_QUEUE_FULL.  Resets the
+ * per-round words (hit, best_depth). */
+int rc_egvm_round_end(const rc_egvm_t *e, const float *values_last, uint64_t max_states, rc_stream_t stream);
+/* For i < n, slot slots[i] (device int32 list) restarts from roots_soa column first_col + i: every worker and `current` hold
+ * that state, counters and queue length are 0, status RC_EGVM_RUNNING or, for the solved cube, RC_EGVM_ROOT_SOLVED.  Other slots
+ * are not touched, nor is anything written for a listed index outside 0 .. n_slots - 1.  Needs stride >= first_col + n. */
+int rc_egvm_plant(const rc_egvm_t *e, const int32_t *slots, uint32_t n, const int8_t *roots_soa, size_t stride, size_t first_col,
+                  rc_stream_t stream);
+
+/* Host only (no GPU needed): the decision tables of one round for n games, drawn from the games' own MT19937 streams exactly as
+ * the reference draws them from np.random (agents.py:694-698): per depth step W doubles as RandomState.random_sample makes them
+ * (two 32-bit outputs each: (a >> 5) * 2^26 + (b >> 6), over 2^53), compared with cdf0 -- what RandomState.choice(2, W, p=[1 - eps,
+ * eps]) does with the normalised cumulative sum of p -- then, for every worker whose double is >= cdf0 and in worker order, an
+ * action as RandomState.randint(0, 12, k) draws it (32-bit outputs masked to 4 bits until one is <= 11).  Game games[i] has its
+ * generator in mt_keys[games[i]][624] / mt_pos[games[i]] (RandomState.get_state()'s key and pos; both are advanced) and plays
+ * in slot slots[i]: table[d * table_stride + slots[i] * W + w] = action 0 .. 11 or RC_EGVM_POLICY.  n_rows: rows of the table
+ * (every slots[i] * W + W must fit; table_stride >= n_rows); n_games: rows of mt_keys. */
+int rc_egvm_draw(uint32_t *mt_keys, int32_t *mt_pos, uint32_t n_games, const int32_t *games, const int32_t *slots, uint32_t n,
+                 double cdf0, uint32_t workers, uint32_t depth, uint8_t *table, size_t table_stride, size_t n_rows);
+
 /* ---- breadth-first search (one problem per call sequence, GPU-wide levels) -----------------------
  *
  * Replaces the FIFO loop of librubiks/solving/agents.py:92-131 (class BFS) with level-synchronous

@@ -23,6 +23,7 @@ from librubiks.cube.device import DeviceCubes
 from librubiks.model import F32_SPLIT, F32_SPLIT_DET, Model, net_fingerprint
 from librubiks.solving import astar_device as ad
 from librubiks.solving import bfs_device as bd
+from librubiks.solving import egvm_device as ed
 from librubiks.solving import mcts_device as md
 from librubiks.solving.results import BatchResult, QueueTable   # noqa: F401  (also this module's names: callers import them from here)
 from librubiks.utils import TickTock
@@ -1071,12 +1072,21 @@ class EGVM(DeepAgent):
     Epsilon-greedy value maximisation (reference agents.py:649-726): `workers` epsilon-greedy policy
     rollouts of `depth` moves from the current state, then jump to the visited state of highest value.
     The random draws follow the reference's np.random call order, so a game is reproducible against
-    it; the workers of a game run in parallel on the device, games run one after another.
+    it; the workers of a game run in parallel on the device.  `search` and a plain `search_batch` play the games one
+    after another on the global stream; `search_batch(..., seeds=, slots=)` advances all games together on the device,
+    each on its own stream (csrc/rubiks_egvm.hip, librubiks/solving/egvm_device.py).
     """
 
-    def __init__(self, net, epsilon: float, workers: int, depth: int, net_dtype=F32_SPLIT):
-        super().__init__(net, net_dtype)
+    def __init__(self, net, epsilon: float, workers: int, depth: int, net_dtype=F32_SPLIT, deterministic: bool = False,
+                 use_graph: bool = True):
+        """deterministic: as for `MCTS` -- one layer plan of the split engine for every row count, so a game of a batched search
+        (`search_batch` with `seeds` or `slots`) does not depend on which other games share its batch.
+        use_graph: the batched search replays a round (D network passes and depth steps) as one captured graph."""
+        super().__init__(net, net_dtype, deterministic)
         self.epsilon, self.workers, self.depth = epsilon, workers, depth
+        self.use_graph = use_graph
+        self.batch = None
+        self.batch_stats = None
 
     @classmethod
     def from_saved(cls, loc: str, use_best: bool, epsilon: float, workers: int, depth: int, **kw):
@@ -1135,7 +1145,145 @@ class EGVM(DeepAgent):
             self.action_queue += deque(int(a) for a in paths[worker, :depth + 1])
         return False
 
-    def search_batch(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
+    def search_batch(self, states, time_limit: float = None, max_states: int = None, seeds=None, slots: int = None) -> BatchResult:
+        """
+        With neither `seeds` nor `slots`: one `search` after the other, drawing from the global np.random stream in the reference's
+        call order.  Otherwise all games advance together on the device (librubiks/solving/egvm_device.py), round by round:
+        game g draws from its own stream np.random.RandomState(seeds[g]) in the reference's order, and ends exactly -- solved
+        flag, len(agent), action queue -- as the reference's `search(states[g])` would right after np.random.seed(seeds[g]),
+        whoever shares the batch and however many slots there are, wherever the network's rows do not depend on the batch (the
+        deterministic engine).  The clock is looked at between rounds only (agents.py:665), and `time_limit` bounds the whole search.
+        seeds: integer array [G], or one integer s for RandomState(s).randint(0, 2**31 - 1, size=G); None (with `slots`): one
+        such call on the global stream at entry.
+        slots: search at most this many games at a time; finished games hand their slots to the scrambles still waiting
+        (continuous batching, as `AStar.search_batch`).  Games that never got a slot before the time limit end unsolved, with 0
+        nodes, status EXHAUSTED and 0 seconds.  `BatchResult.iterations` is the number of rounds per game.
+        """
+        if seeds is None and slots is None:
+            return self._search_serial(states, time_limit, max_states)
+        roots = DeviceCubes.of(states)
+        seeds = ed.game_seeds(seeds, roots.n)
+        time_limit, max_states = self.reset(time_limit, max_states)
+        return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
+
+    def _batch_for(self, n_slots: int, queue_width: int) -> "ed.EGVMBatch":
+        b = self.batch
+        if b is None or (b.S, b.W, b.D, b.use_graph) != (n_slots, self.workers, self.depth, bool(self.use_graph)) \
+                or b.Q < queue_width or b.Q > 4 * queue_width:
+            self.batch = None
+            torch.cuda.empty_cache()
+            b = self.batch = ed.EGVMBatch(n_slots, self.workers, self.depth, queue_width, use_graph=self.use_graph)
+        b.set_net(self._search_net(), self.net_dtype)   # every search: `net` may have been trained or replaced since the last one
+        return b
+
+    QUEUE_ROUNDS = 64   # queue rows of a search bounded by time only start at this many rounds and double between rounds
+
+    @no_grad
+    def _search_lockstep(self, roots: DeviceCubes, time_limit: float, max_states: int, seeds: np.ndarray, slots) -> BatchResult:
+        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given)."""
+        W, D = self.workers, self.depth
+        cap = int(max_states)
+        by_states = not _unbounded(max_states)
+        rounds_cap = ed.queue_rounds(cap, W, D)           # rounds a game can complete (agents.py:665)
+        # (no round fits: every game is planted at once, so that solved scrambles are seen -- agents.py:661 comes before :665)
+        pool = SlotPool(roots.n, slots if rounds_cap >= 1 else None, self.tt.tock)
+        S, owner = pool.S, pool.owner
+        batch = self._batch_for(S, D * max(1, rounds_cap if by_states else self.QUEUE_ROUNDS))
+        cdf0 = ed.choice_cdf(self.epsilon)
+        streams = ed.GameStreams(seeds)                   # every game's own np.random stream, started when the game is planted
+        tables = [torch.full((D, batch.R16), ed.POLICY, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        views = [t.numpy() for t in tables]
+        played = np.zeros(S, dtype=np.int64)              # rounds queued for the slot's game so far
+        stats = self.batch_stats = {"rounds": 0, "draw_s": 0.0, "draw_exposed_s": 0.0, "wait_s": 0.0, "device_round_ms": []}
+
+        def draw(into, which):
+            """The next round's decisions of the games in slots `which`."""
+            t0 = perf_counter()
+            streams.draw(owner[which], which, cdf0, W, D, into, batch.R)
+            dt = perf_counter() - t0
+            stats["draw_s"] += dt
+            return dt
+
+        def adopt(which):
+            streams.start(owner[which])
+            played[which] = 0
+
+        def plant(into, first):
+            batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first)
+        self.tt.tick()
+        batch.reset(roots)                                # the first S scrambles; the others move in as games finish
+        words = batch.snapshot()
+        adopt(np.arange(S))
+        words[1].synchronize()
+        status = words[0][0].numpy().copy()               # (root-solved games are known before the first round)
+        taken, r = [], 0
+        final = words[0].numpy().copy()
+        if rounds_cap >= 1 and ((status == ed.RUNNING).any() or pool.waiting):
+            stats["draw_exposed_s"] += draw(views[0], np.flatnonzero(status == ed.RUNNING))
+            while True:
+                if not by_states:
+                    batch.grow_queues(D * int(played.max() + 1))
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                batch.round(tables[r % 2], cap)
+                t1.record()
+                host, ev = batch.snapshot()
+                live = owner >= 0
+                played[live & (status == ed.RUNNING)] += 1
+                # round r + 1 is drawn while round r runs: for every game that can still be running then (a hit ends it sooner:
+                # those draws are ones the reference would not have made, of a game that is over)
+                go_on = np.flatnonzero(live & (status == ed.RUNNING) & (played < rounds_cap))
+                draw(views[(r + 1) % 2], go_on)
+                t_wait = perf_counter()
+                ev.synchronize()
+                stats["wait_s"] += perf_counter() - t_wait
+                stats["device_round_ms"].append(t0.elapsed_time(t1))
+                stats["rounds"] = r = r + 1
+                final = host.numpy().copy()
+                status = final[0]
+                if (status == ed.QUEUE_FULL).any():
+                    raise _hip.RubiksHipError(f"EGVM: the queue row of slot {int(np.argmax(status == ed.QUEUE_FULL))} is full "
+                                              f"({batch.Q} bytes, {int(played.max())} rounds)")
+                now = self.tt.tock()
+                ended = live & (status != ed.RUNNING)
+                done = np.flatnonzero(ended)
+                pool.sighted(done, now)
+                if now >= time_limit or not (live & ~ended).any() and not pool.waiting:
+                    break
+                if pool.waiting and len(done):
+                    # the finished slots' results leave without waiting, then the waiting scrambles are planted there
+                    taken.append((owner[done].copy(), final[:, done].copy(), batch.take_queues(done, final[2, done].max())))
+                    fresh = pool.refill(done, plant)
+                    adopt(fresh)
+                    status[done] = ed.EXHAUSTED           # (an empty slot is not played)
+                    status[fresh] = ed.RUNNING            # (a solved scramble shows ROOT_SOLVED in the next block; its draws are not used)
+                    stats["draw_exposed_s"] += draw(views[r % 2], fresh)
+        torch.cuda.synchronize()
+        if self._overflowed(batch.engine):   # the split engine could not represent an activation: the same search (same seeds) in fp32
+            return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
+        seconds = self.tt.tock()
+        left = np.flatnonzero(owner >= 0)
+        parts = [(games, self._part(w, q[0], q[1])) for games, w, q in taken]
+        if len(left):
+            w = final[:, left]
+            parts.append((owner[left], self._part(w, *batch.take_queues(left, w[2].max())[:2])))
+        result = BatchResult.merge(pool.n_games, parts, seconds)
+        if rounds_cap < 1:                                # agents.py:665 is false before the first round
+            result.status[result.status == ed.RUNNING] = ed.EXHAUSTED
+        pool.close(result, seconds, ed.EXHAUSTED)
+        self._explored_states = int(result.nodes[0])
+        self.action_queue = result.queues[0]
+        return result
+
+    @staticmethod
+    def _part(words: np.ndarray, host: torch.Tensor, ev) -> BatchResult:
+        ev.synchronize()
+        status, nodes, qlen, rounds = words
+        solved = (status == ed.SOLVED) | (status == ed.ROOT_SOLVED)
+        return BatchResult(solved, np.where(solved, qlen, -1), nodes.copy(), QueueTable(host.numpy().copy(), qlen), 0.0, rounds.copy(),
+                           status.copy())
+
+    def _search_serial(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
         states = states.numpy() if isinstance(states, DeviceCubes) else np.asarray(states)
         solved, lengths, nodes, queues = [], [], [], []
         tt = TickTock()

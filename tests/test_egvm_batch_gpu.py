@@ -1,0 +1,353 @@
+"""
+The batched EGVM search (`EGVM.search_batch(..., seeds=, slots=)`, rc_egvm_step / rc_egvm_round_end / rc_egvm_plant): game g of a
+batch ends exactly as the oracle's `search(states[g])` right after np.random.seed(seeds[g]) -- whoever shares the batch, however
+many slots there are, replayed from a captured graph or launched one by one; the serial path (neither keyword) still consumes the
+global stream as `search` after `search` does; the pooled Evaluator draws today's scrambles; and with trained weights the batched
+form solves what the serial form solves, in less wall time.
+"""
+import os
+import time
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from conftest import GOLDEN, ROOT  # noqa: E402
+from oracle import agents as oa  # noqa: E402  (checker only)
+from oracle import cube as oc  # noqa: E402
+
+WEIGHTS = os.path.join(ROOT, "weights", "fc_small_r1")
+ROOT_SOLVED, FIRST_ROUND, LATER_ROUND, UNSOLVED = "root-solved", "solved in the first round", "solved in a later round", "unsolved"
+
+# (seed of the inputs, games, scramble depth of game i, indices of solved scrambles, eps, W, D, max_states, kinds the set produces).
+# The first is the set the batched search's definition was checked on: the oracle gives 1 / 19 / 9 / 31 games of the four kinds.
+# The others cover eps 0 (every worker follows the policy: the stand-in net, whose policy is arbitrary, solves nothing, so the
+# set can produce root-solved and unsolved games only), eps 1 with D = 1 and W = 21 (not a multiple of 16 or 4), and W 50, D 3.
+MAIN = (11, 60, lambda i: 1 + i % 4, (7,), 0.375, 32, 8, 2048, None)
+MORE = [(12, 40, lambda i: 1 + i % 3, (7, 20), 0.0, 5, 6, 150, (ROOT_SOLVED, UNSOLVED)),
+        (13, 40, lambda i: 1 + i % 3, (7, 20), 1.0, 21, 1, 126, (ROOT_SOLVED, FIRST_ROUND, LATER_ROUND, UNSOLVED)),
+        (15, 40, lambda i: 1 + i % 5, (7, 20), 0.5, 50, 3, 600, (ROOT_SOLVED, FIRST_ROUND, LATER_ROUND, UNSOLVED))]
+
+
+def inputs(seed, n, depth_of, solved_at):
+    np.random.seed(seed)
+    states = np.array([oc.scramble(depth_of(i), True)[0] for i in range(n)])
+    for i in solved_at:
+        states[i] = oc.get_solved()
+    seeds = np.random.randint(0, 2 ** 31 - 1, n)
+    return states, seeds
+
+
+def oracle_games(onet, states, seeds, eps, W, D, cap):
+    """[(solved, nodes, queue)] of the oracle's search of every game right after np.random.seed(seed)."""
+    out = []
+    for s, seed in zip(states, seeds):
+        np.random.seed(int(seed))
+        ref = oa.EGVM(onet, eps, W, D)
+        ok = ref.search(s, cap)
+        out.append((bool(ok), len(ref), [int(a) for a in ref.action_queue]))
+    return out
+
+
+def kind_of(solved, nodes, W, D):
+    if solved:
+        return ROOT_SOLVED if nodes == 0 else FIRST_ROUND if nodes <= W * D else LATER_ROUND
+    return UNSOLVED
+
+
+def games_of(res):
+    return [(bool(res.solved[g]), int(res.nodes[g]), list(res.queues[g])) for g in range(len(res.solved))]
+
+
+def replay(states, queues):
+    """Every game's queue applied to its scramble (oracle moves)."""
+    out = []
+    for s, q in zip(states, queues):
+        s = s.copy()
+        for a in q:
+            s = oc.multi_rotate_actions(s[None], np.array([a]))[0]
+        out.append(s)
+    return np.array(out)
+
+
+@pytest.fixture(scope="module")
+def net_gpu(standin_net):
+    return standin_net.cuda()
+
+
+@pytest.fixture(scope="module")
+def trained():
+    from librubiks.model import Model
+    return Model.load(WEIGHTS).cuda().eval()
+
+
+def _agent(net, eps, W, D, **kw):
+    from librubiks.solving.agents import EGVM
+    kw.setdefault("net_dtype", torch.float32)
+    return EGVM(net, eps, W, D, **kw)
+
+
+def _check_set(net_gpu, spec):
+    from librubiks.solving import egvm_device as ed
+    seed, n, depth_of, solved_at, eps, W, D, cap, kinds = spec
+    states, seeds = inputs(seed, n, depth_of, solved_at)
+    want = oracle_games(oa.TorchNet(net_gpu, device="cuda"), states, seeds, eps, W, D, cap)
+    res = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=seeds)
+    got = games_of(res)
+    for g in range(n):
+        assert got[g] == want[g], f"game {g} (eps {eps}, W {W}, D {D})"
+        assert res.lengths[g] == (len(want[g][2]) if want[g][0] else -1)
+    won = np.flatnonzero(res.solved)
+    assert (replay(states[won], [got[g][2] for g in won]) == oc.get_solved()).all()
+    assert (res.status[list(solved_at)] == ed.ROOT_SOLVED).all() and (res.nodes[list(solved_at)] == 0).all()
+    assert (res.iterations == -(-res.nodes // (W * D))).all()               # rounds per game: a hit ends its round early
+    count = {}
+    for ok, nodes, _ in want:
+        k = kind_of(ok, nodes, W, D)
+        count[k] = count.get(k, 0) + 1
+    return count
+
+
+def test_parity_on_the_checked_inputs(net_gpu):
+    count = _check_set(net_gpu, MAIN)
+    print("kinds:", count)
+    assert count.get(ROOT_SOLVED) == 1
+    for k in (FIRST_ROUND, LATER_ROUND, UNSOLVED):      # the set is not degenerate
+        assert count.get(k, 0) >= 5, count
+
+
+@pytest.mark.parametrize("spec", MORE, ids=["eps0", "eps1_D1_W21", "W50_D3"])
+def test_parity_on_more_parameter_sets(net_gpu, spec):
+    count = _check_set(net_gpu, spec)
+    print("kinds:", count)
+    assert set(count) == set(spec[-1]), count
+    for k in spec[-1]:
+        assert count[k] >= 2, count
+
+
+def test_no_round_fits(net_gpu):
+    """max_states below W D: the reference's loop test (agents.py:665) fails before the first round."""
+    from librubiks.solving import egvm_device as ed
+    states, seeds = inputs(5, 6, lambda i: 2 + i, (5,))
+    want = oracle_games(oa.TorchNet(net_gpu, device="cuda"), states, seeds, 0.375, 8, 5, 39)
+    res = _agent(net_gpu, 0.375, 8, 5).search_batch(states, None, 39, seeds=seeds, slots=4)   # (the solved scramble is beyond the slots)
+    assert games_of(res) == want == [(g == 5, 0, []) for g in range(6)]
+    assert res.status.tolist() == [ed.ROOT_SOLVED if g == 5 else ed.EXHAUSTED for g in range(6)] and (res.iterations == 0).all()
+
+
+def test_pooling(net_gpu):
+    from librubiks.solving import egvm_device as ed
+    _, n, depth_of, solved_at, eps, W, D, cap, _ = MAIN
+    states, seeds = inputs(MAIN[0], n, depth_of, solved_at)
+    plain = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=seeds)
+    for slots in (n, 16, 5, 1):
+        res = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=seeds, slots=slots)
+        assert games_of(res) == games_of(plain), f"slots {slots}"
+        for k in ("lengths", "iterations", "status"):
+            assert np.array_equal(getattr(res, k), getattr(plain, k)), (slots, k)
+        assert (res.game_seconds > 0).all() and (res.game_seconds <= res.seconds).all()
+        if slots < n:
+            assert (res.game_seconds[slots:] < res.seconds).all() and res.game_seconds[slots:].mean() < res.seconds
+    # seeds=None with slots: one draw of G seeds from the global stream at entry
+    np.random.seed(77)
+    a = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, slots=16)
+    after = np.random.get_state()
+    np.random.seed(77)
+    drawn = np.random.randint(0, 2 ** 31 - 1, size=n)
+    assert np.array_equal(np.random.get_state()[1], after[1])
+    assert games_of(a) == games_of(_agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=drawn))
+    # one integer: the documented expansion
+    b = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=5)
+    c = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=np.random.RandomState(5).randint(0, 2 ** 31 - 1, size=n))
+    assert games_of(b) == games_of(c)
+    # a pool bounded by time: games that never got a slot end as A*'s do
+    np.random.seed(3)
+    deep = np.array([oc.scramble(20, True)[0] for _ in range(200)])
+    agent = _agent(net_gpu, eps, W, D)
+    agent.search_batch(deep[:4], None, 20_000, seeds=1, slots=4)             # engine, batch and captured round set up outside the timed search
+    limit = 0.5
+    t0 = time.perf_counter()
+    res = agent.search_batch(deep, limit, 20_000, seeds=1, slots=4)
+    wall = time.perf_counter() - t0
+    never = (res.nodes == 0) & (res.status == ed.EXHAUSTED)
+    assert never.sum() > 100 and not res.solved[never].any() and (res.lengths[never] == -1).all()
+    assert (res.game_seconds[never] == 0).all() and (res.game_seconds[~never] > 0).all()
+    assert res.seconds < limit + 0.25 and wall < limit + 0.5, (res.seconds, wall)
+
+
+def test_captured_rounds(net_gpu):
+    from librubiks.solving.agents import EGVM
+    _, n, depth_of, solved_at, eps, W, D, cap, _ = MAIN
+    states, seeds = inputs(MAIN[0], n, depth_of, solved_at)
+    with_graph = _agent(net_gpu, eps, W, D, use_graph=True)
+    res_g = with_graph.search_batch(states, None, cap, seeds=seeds)
+    assert with_graph.batch._graphs                                          # rounds were replayed from a captured graph
+    without = _agent(net_gpu, eps, W, D, use_graph=False)
+    res_e = without.search_batch(states, None, cap, seeds=seeds)
+    assert not without.batch._graphs
+    assert games_of(res_g) == games_of(res_e)
+    assert np.array_equal(res_g.iterations, res_e.iterations) and np.array_equal(res_g.status, res_e.status)
+    # bounded by time only: the queue rows start at QUEUE_ROUNDS rounds and double between rounds
+    np.random.seed(9)
+    deep = np.array([oc.scramble(30, True)[0] for _ in range(12)])
+    agent = _agent(net_gpu, 0.375, 4, 2)
+    res = agent.search_batch(deep, 0.6, None, seeds=3)
+    rounds = res.iterations
+    print("time-only rounds:", rounds.tolist(), "queue width", agent.batch.Q)
+    assert rounds.max() > 2 * EGVM.QUEUE_ROUNDS and agent.batch.Q >= 2 * rounds.max()
+    assert (res.nodes[~res.solved] == rounds[~res.solved] * 4 * 2).all()
+    lens = np.array([len(q) for q in res.queues])
+    assert (lens >= rounds).all() and (lens <= 2 * rounds).all()
+    held = agent.batch.current.cpu().numpy()
+    ends = replay(deep, [list(q) for q in res.queues])
+    for g in range(len(deep)):                                               # every queue replays to the state the slot holds
+        assert np.array_equal(ends[g], oc.get_solved() if res.solved[g] else held[g]), f"game {g}"
+
+
+def test_chunked_network_passes(net_gpu, trained, monkeypatch):
+    """More rows than one network call takes (NET_CHUNK): the head of a step is assembled from several calls, with the same results."""
+    from librubiks.model import F32_SPLIT
+    from librubiks.solving import egvm_device as ed
+    _, n, depth_of, solved_at, eps, W, D, cap, _ = MAIN
+    states, seeds = inputs(MAIN[0], n, depth_of, solved_at)
+    whole = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=seeds)
+    d12, s12 = _depth12(32)
+    whole_t = _agent(trained, 0.375, 10, 50, net_dtype=F32_SPLIT, deterministic=True).search_batch(d12, None, 5_000, seeds=s12)
+    monkeypatch.setattr(ed, "NET_CHUNK", 256)
+    parts = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=seeds)          # 1 920 rows: 8 calls (one-hot input)
+    assert games_of(parts) == games_of(whole)
+    monkeypatch.setattr(ed, "NET_CHUNK", 128)
+    parts_t = _agent(trained, 0.375, 10, 50, net_dtype=F32_SPLIT, deterministic=True).search_batch(d12, None, 5_000, seeds=s12)
+    assert games_of(parts_t) == games_of(whole_t) and whole_t.solved.sum() > 0            # 320 rows: 128 + 128 + 64 (cube input)
+    fast = _agent(trained, 0.375, 10, 50, net_dtype=torch.bfloat16).search_batch(d12, None, 5_000, seeds=s12)
+    won = np.flatnonzero(fast.solved)
+    assert len(won) and (replay(d12[won], [list(fast.queues[g]) for g in won]) == oc.get_solved()).all()
+
+
+def test_serial_path_untouched(net_gpu):
+    g = np.load(f"{GOLDEN}/simple_agents_golden.npz")
+    cases = sorted(k[:-len("params")] for k in g.files if k.startswith("egvm_") and k.endswith("params"))
+    sdepth = {0: 3, 1: 4, 2: 2, 3: 5, 4: 20, 5: 1, 6: 2}
+    assert len(cases) >= 5
+    for pre in cases:                                                         # the reference's recorded runs, through search_batch
+        eps, workers, depth, max_states, solved, n, seed = g[pre + "params"]
+        np.random.seed(int(seed))
+        state, _, _ = oc.scramble(sdepth[int(pre.split("_")[1])], True)
+        agent = _agent(net_gpu, float(eps), int(workers), int(depth))
+        res = agent.search_batch(state[None], None, int(max_states))
+        assert games_of(res) == [(bool(solved), int(n), list(g[pre + "queue"]))], pre
+    # several games: the global stream is consumed as by `search` after `search`
+    np.random.seed(6)
+    states = np.array([oc.scramble(1 + i % 4, True)[0] for i in range(10)])
+    np.random.seed(123)
+    res = _agent(net_gpu, 0.375, 8, 5).search_batch(states, None, 400)
+    after = np.random.get_state()
+    np.random.seed(123)
+    one = _agent(net_gpu, 0.375, 8, 5)
+    want = []
+    for s in states:
+        ok = one.search(s, None, 400)
+        want.append((bool(ok), len(one), list(one.action_queue)))
+    assert games_of(res) == want
+    assert np.array_equal(np.random.get_state()[1], after[1]) and np.random.get_state()[2] == after[2]
+    assert sum(w[0] for w in want) >= 2 and sum(not w[0] for w in want) >= 2
+
+
+def test_evaluator_joins_the_pool(net_gpu):
+    from librubiks.solving.evaluation import Evaluator
+    games, depths, cap = 12, [1, 3], 600
+    np.random.seed(21)
+    res0, states0, times0 = Evaluator(games, depths, None, cap).eval(_agent(net_gpu, 0.375, 10, 5))
+    drawn = []
+    agent = _agent(net_gpu, 0.375, 10, 5)
+    inner = agent.search_batch
+    agent.search_batch = lambda states, *a, **kw: (drawn.append(states.numpy()), inner(states, *a, **kw))[1]
+    agent.search_batch.__signature__ = __import__("inspect").signature(inner)
+    np.random.seed(21)
+    ev = Evaluator(games, depths, None, cap, slots=8)
+    res1, states1, times1 = ev.eval(agent)
+    np.random.seed(21)
+    want = np.concatenate([[oc.scramble(d, True)[0] for _ in range(games)] for d in depths])
+    assert len(drawn) == 1 and np.array_equal(drawn[0], want)                 # today's scrambles, all depths in one pool
+    assert res1.shape == states1.shape == times1.shape == res0.shape == (len(depths), games)
+    assert len(ev.batch_seconds) == 1 and (times1 > 0).all() and (times1 <= ev.batch_seconds[0]).all()
+    assert ((res1 >= 0) | (res1 == -1)).all() and (states1[res1 == -1] == cap // 50 * 50).all()
+
+
+def _depth12(n=128):
+    np.random.seed(12)
+    states = np.array([oc.scramble(12, True)[0] for _ in range(n)])
+    return states, np.random.randint(0, 2 ** 31 - 1, n)
+
+
+@pytest.mark.parametrize("dtype_name", ["f32s", "bf16"])
+def test_trained_weights(trained, dtype_name):
+    """128 depth-12 scrambles, W 10, D 50, max_states 20 000.  Reported, not asserted: the share of games identical to the serial
+    search (a near-tie in an argmax may fall the other way when a row's summation order changes with the row count)."""
+    from librubiks import cube
+    from librubiks.model import F32_SPLIT
+    from librubiks.utils import bernoulli_error
+    dt = {"f32s": F32_SPLIT, "bf16": torch.bfloat16}[dtype_name]
+    states, seeds = _depth12()
+    eps, W, D, cap = 0.375, 10, 50, 20_000
+    batched = _agent(trained, eps, W, D, net_dtype=dt).search_batch(states, None, cap, seeds=seeds)
+    won = np.flatnonzero(batched.solved)
+    acts, lens = batched.queues.padded(won)
+    x = states[won].copy()
+    for j in range(acts.shape[1]):
+        move = lens > j
+        x[move] = cube.multi_rotate(x[move], *cube.indices_to_actions(acts[move, j].astype(np.int64)))
+    assert cube.multi_is_solved(x).all()                                      # every reported solution replays
+    serial_agent = _agent(trained, eps, W, D, net_dtype=dt)
+    serial = []
+    for s, seed in zip(states, seeds):
+        np.random.seed(int(seed))
+        ok = serial_agent.search(s, None, cap)
+        serial.append((bool(ok), len(serial_agent), list(serial_agent.action_queue)))
+    rate_s, rate_b = np.mean([w[0] for w in serial]), batched.solved.mean()
+    same = np.mean([a == b for a, b in zip(games_of(batched), serial)])
+    print(f"EGVM {dtype_name}: solve rate serial {rate_s:.4f}, batched {rate_b:.4f}; games identical to the serial search: {same:.4f}")
+    assert abs(rate_b - rate_s) <= bernoulli_error(rate_s, len(states), 0.05), (rate_s, rate_b)
+
+
+def test_trained_deterministic_is_batch_independent(trained):
+    states, seeds = _depth12()
+    eps, W, D, cap = 0.375, 10, 50, 20_000
+    mk = lambda: _agent(trained, eps, W, D, net_dtype=__import__("librubiks.model").model.F32_SPLIT, deterministic=True)   # noqa: E731
+    plain = mk().search_batch(states, None, cap, seeds=seeds)
+    pooled = mk().search_batch(states, None, cap, seeds=seeds, slots=16)
+    assert games_of(pooled) == games_of(plain)
+    assert np.array_equal(pooled.iterations, plain.iterations) and np.array_equal(pooled.status, plain.status)
+    alone, want = mk(), games_of(plain)
+    for g in range(len(states)):
+        one = alone.search_batch(states[g:g + 1], None, cap, seeds=seeds[g:g + 1])
+        assert games_of(one) == [want[g]], f"game {g}"
+    assert 0 < plain.solved.sum()
+
+
+def test_batched_form_takes_less_wall_time(trained):
+    """64 depth-20 scrambles at W 10, D 50 on the default engine, serial and batched in one process after a warm-up of both.
+    max_states 5 000 (10 rounds per game) keeps the serial form to seconds; the forms' ratio does not depend on it: the serial
+    form pays 2 D host round trips per game and round, the batched form one per round for all games."""
+    np.random.seed(20)
+    states = np.array([oc.scramble(20, True)[0] for _ in range(64)])
+    seeds = np.random.randint(0, 2 ** 31 - 1, 64)
+    agent = _agent(trained, 0.375, 10, 50, net_dtype=__import__("librubiks.model").model.F32_SPLIT)
+    agent.search_batch(states[:2], None, 1_000)                               # warm-up: serial ...
+    agent.search_batch(states, None, 5_000, seeds=seeds)                      # ... and batched (engine, batch, captured round)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    np.random.seed(1)
+    serial = agent.search_batch(states, None, 5_000)
+    torch.cuda.synchronize()
+    t_serial = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    batched = agent.search_batch(states, None, 5_000, seeds=seeds)
+    torch.cuda.synchronize()
+    t_batched = time.perf_counter() - t0
+    print(f"64 games, W 10, D 50, max_states 5 000: serial {t_serial:.3f} s ({serial.nodes.sum()} states), "
+          f"batched {t_batched:.3f} s ({batched.nodes.sum()} states); stats {agent.batch_stats['rounds']} rounds, "
+          f"draw {agent.batch_stats['draw_s']:.3f} s, wait {agent.batch_stats['wait_s']:.3f} s")
+    assert t_batched < t_serial, (t_batched, t_serial)
