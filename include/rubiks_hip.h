@@ -704,6 +704,71 @@ int rc_bfs_commit(const rc_bfs_t *b, uint32_t lo, uint32_t n_parents, uint32_t n
 int rc_bfs_path(const rc_bfs_t *b, uint32_t node, uint8_t *out_actions, uint32_t *out_len, uint32_t max_len,
                 rc_stream_t stream);
 
+/* ---- the 6x8x6 representation (csrc/rubiks_env686.hip) -------------------------------------------------------------
+ * The reference's second representation (librubiks/cube/cube.py:67-71,311-388): a state is int8[6][8][6], the one-hot colour of
+ * the 8 non-centre stickers of each face.  Device form: 48 int8 planes of sticker colour 0..5, plane f*8+p = sticker p of face f
+ * (so the one-hot index of the network input is (f*8+p)*6 + colour), structure-of-arrays under the rules of the 20 code planes
+ * above (*_soa686: soa686[s * stride + i], stride a multiple of 16 and >= round_up(n, 16)).  Every action is one permutation of
+ * the 48 stickers; the two representations are isomorphic, so searches keep 20-byte states and cross the bridge only for the
+ * network input.
+ *
+ * Host-side copies of the tables (no GPU needed), both derived at compile time from the 20x24 move table and the sticker layout:
+ *   out576[a*48 + s]                 = the sticker that action a moves onto sticker s
+ *   out2880[((i*24 + v)*3 + k)*2 ..] = (sticker, colour) pair k of cubie i with code v; sticker 255 = no such pair (edges have 2) */
+int rc686_get_perm_table(uint8_t *out576);
+int rc686_get_bridge_table(uint8_t *out2880);
+
+/* The reference's (n,6,8,6) int8 one-hot arrays (row-major, 288 bytes per state) <-> sticker planes. */
+int rc686_aos_to_soa(const int8_t *oh_aos, int8_t *soa686, size_t n, size_t stride, rc_stream_t stream);
+int rc686_soa_to_aos(const int8_t *soa686, int8_t *oh_aos, size_t n, size_t stride, rc_stream_t stream);
+
+/* out[i] = move actions[i] on in[i].  Replaces _Cube686.multi_rotate, a Python loop over the states
+ * (librubiks/cube/cube.py:349-361; one state: :330-347).  in and out may alias exactly.  Algorithmic HBM bytes: 97 per state. */
+int rc686_multi_rotate(const int8_t *in_soa686, const uint8_t *actions, int8_t *out_soa686, size_t n, size_t stride_in,
+                       size_t stride_out, rc_stream_t stream);
+/* children[12p + k] = action k on parents[p], as rc_expand12 / rc_expand12_flags (librubiks/solving/agents.py:277-281,513;
+ * librubiks/train.py:285-296 with cube.py:349-361 underneath).  Same flag buffers as rc_expand12_flags. */
+int rc686_expand12(const int8_t *parents_soa686, int8_t *children_soa686, size_t n_parents, size_t stride_p, size_t stride_c,
+                   rc_stream_t stream);
+int rc686_expand12_flags(const int8_t *parents_soa686, int8_t *children_soa686, size_t n_parents, size_t stride_p, size_t stride_c,
+                         uint8_t *parent_solved, uint8_t *child_solved, rc_stream_t stream);
+/* flags[i] = 1 iff every sticker of state i has its face's colour (multi_is_solved, librubiks/cube/cube.py:85-89 against
+ * _get_686solved :67-71); flags holds round_up(n, 16) bytes. */
+int rc686_is_solved(const int8_t *soa686, uint8_t *flags, size_t n, size_t stride, rc_stream_t stream);
+/* (n, 288) one-hot network input, every element written.  Replaces _Cube686.as_oh (librubiks/cube/cube.py:363-369).
+ * Algorithmic HBM bytes: 1200 (f32) / 624 (bf16) per state. */
+int rc686_as_oh_f32(const int8_t *soa686, float *out, size_t n, size_t stride, rc_stream_t stream);
+int rc686_as_oh_bf16(const int8_t *soa686, uint16_t *out, size_t n, size_t stride, rc_stream_t stream);
+/* (n, 6, 8) float32: +1 where a sticker has its face's colour, -1 elsewhere.  Replaces _Cube686.as_correct
+ * (librubiks/cube/cube.py:372-380, dispatcher :135-137) from the states themselves. */
+int rc686_as_correct_f32(const int8_t *soa686, float *out, size_t n, size_t stride, rc_stream_t stream);
+/* In place: cube i <- action moves[d * moves_stride + i] for d = 0 .. depth-1 (scramble's rotate loop,
+ * librubiks/cube/cube.py:206-211); action 12 is the identity. */
+int rc686_apply_moves(int8_t *soa686, const uint8_t *moves, size_t n, size_t stride, size_t moves_stride, size_t depth,
+                      rc_stream_t stream);
+
+/* Small calls on the reference's own (n,6,8,6) int8 one-hot layout: one launch each, pointers may be pinned host memory mapped
+ * into the device, no alignment requirement (as the *_aos calls of the 20x24 representation).  in and out must differ.
+ *   rc686_multi_rotate_aos   librubiks/cube/cube.py:330-361      rc686_is_solved_aos   :85-89      rc686_as_oh_aos_f32   :363-369 */
+int rc686_multi_rotate_aos(const int8_t *in_aos, const uint8_t *actions, int8_t *out_aos, size_t n, rc_stream_t stream);
+int rc686_is_solved_aos(const int8_t *in_aos, uint8_t *flags, size_t n, rc_stream_t stream);
+int rc686_as_oh_aos_f32(const int8_t *in_aos, float *out, size_t n, rc_stream_t stream);
+
+/* The bridge from the 20 code planes (`soa` as everywhere above; a column window of a batch is soa + lo with lo % 16 == 0):
+ *   rc_2024_to_686               the 48 sticker planes of the same cubes
+ *   rc_as_oh686_from2024_*       _Cube686.as_oh (cube.py:363-369) of the same cubes, (n, 288): the agents' encoder for a network with
+ *                                is2024 = false, one launch, no sticker planes in HBM
+ *   rc_as_correct_from2024_f32   _Cube686.as_correct (cube.py:372-380) of the same cubes, (n, 6, 8) */
+int rc_2024_to_686(const int8_t *soa, int8_t *soa686, size_t n, size_t stride, size_t stride686, rc_stream_t stream);
+int rc_as_oh686_from2024_f32(const int8_t *soa, float *out, size_t n, size_t stride, rc_stream_t stream);
+int rc_as_oh686_from2024_bf16(const int8_t *soa, uint16_t *out, size_t n, size_t stride, rc_stream_t stream);
+int rc_as_correct_from2024_f32(const int8_t *soa, float *out, size_t n, size_t stride, rc_stream_t stream);
+
+/* (n, 288) one-hot network input -> (n, 6, 8) correctness in the same dtype: cube.as_correct as ConvNet.forward calls it on its
+ * input (librubiks/model.py:326 -> librubiks/cube/cube.py:135-137,372-380). */
+int rc686_as_correct_oh_f32(const float *oh, float *out, size_t n, rc_stream_t stream);
+int rc686_as_correct_oh_bf16(const uint16_t *oh, uint16_t *out, size_t n, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,28 @@ SIGNATURES = {
     "rc_head_bf16": [P, SZ, SZ, P, P, SZ, P, I, ctypes.c_float, P],
     "rc_adi_targets": [P, P, P, SZ, SZ, ctypes.c_float, I, P, P, P],
     "rc_first_layer_mfma_bf16": [P, SZ, SZ, P, P, P, SZ, I, ctypes.c_float, I, P],
+    # the 6x8x6 representation (csrc/rubiks_env686.hip)
+    "rc686_get_perm_table": [P],
+    "rc686_get_bridge_table": [P],
+    "rc686_aos_to_soa": [P, P, SZ, SZ, P],
+    "rc686_soa_to_aos": [P, P, SZ, SZ, P],
+    "rc686_multi_rotate": [P, P, P, SZ, SZ, SZ, P],
+    "rc686_expand12": [P, P, SZ, SZ, SZ, P],
+    "rc686_expand12_flags": [P, P, SZ, SZ, SZ, P, P, P],
+    "rc686_is_solved": [P, P, SZ, SZ, P],
+    "rc686_as_oh_f32": [P, P, SZ, SZ, P],
+    "rc686_as_oh_bf16": [P, P, SZ, SZ, P],
+    "rc686_as_correct_f32": [P, P, SZ, SZ, P],
+    "rc686_apply_moves": [P, P, SZ, SZ, SZ, SZ, P],
+    "rc686_multi_rotate_aos": [P, P, P, SZ, P],
+    "rc686_is_solved_aos": [P, P, SZ, P],
+    "rc686_as_oh_aos_f32": [P, P, SZ, P],
+    "rc_2024_to_686": [P, P, SZ, SZ, SZ, P],
+    "rc_as_oh686_from2024_f32": [P, P, SZ, SZ, P],
+    "rc_as_oh686_from2024_bf16": [P, P, SZ, SZ, P],
+    "rc_as_correct_from2024_f32": [P, P, SZ, SZ, P],
+    "rc686_as_correct_oh_f32": [P, P, SZ, P],
+    "rc686_as_correct_oh_bf16": [P, P, SZ, P],
 }
 _RESTYPES = {"rc_error_string": c_char_p, "rc_split_layer_struct_bytes": c_size_t}
 

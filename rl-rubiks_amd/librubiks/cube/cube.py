@@ -7,7 +7,8 @@ runs as a HIP kernel behind include/rubiks_hip.h: the arrays are transposed into
 at the boundary (DeviceCubes), so callers that care about throughput should stay on the device
 (`DeviceCubes`, `scramble_batch`, the batched agents) instead of bouncing through NumPy per call.
 
-Only the 20x24 representation exists (north_star scope); `set_is2024(False)` raises.
+This module is the 20x24 representation.  The reference's other one, 6x8x6, is the namespace `librubiks.cube.cube686` (same
+function names) and `ModelConfig(is2024=False)` for networks; the process-wide switch `set_is2024(False)` stays refused.
 """
 import numpy as np
 import torch
@@ -146,7 +147,8 @@ _stored_repr = True
 def set_is2024(is2024: bool):
     assert type(is2024) is bool
     if not is2024:
-        raise NotImplementedError("only the 20x24 (int8 corner/edge) representation is implemented on MI355X")
+        raise NotImplementedError("this module is the 20x24 representation and has no process-wide switch: the 6x8x6 functions are "
+                                  "librubiks.cube.cube686, and a network chooses its input with ModelConfig(is2024=False)")
 
 
 def get_is2024():
@@ -175,7 +177,7 @@ def shape():
 
 def as_correct(t):
     """Reference cube.py:135-137: the conv net's input form, defined for the 6x8x6 representation only."""
-    raise NotImplementedError("as_correct belongs to the 6x8x6 representation, which is out of scope on MI355X")
+    raise NotImplementedError("as_correct belongs to the 6x8x6 representation: use librubiks.cube.cube686.as_correct")
 
 
 def get_oh_shape() -> int:

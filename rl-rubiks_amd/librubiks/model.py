@@ -26,6 +26,7 @@ from librubiks import gpu
 from librubiks.utils import NullLogger
 
 OH_WIDTH = 480
+OH_WIDTH_686 = 288   # the 6x8x6 representation's one-hot (ModelConfig(is2024=False); librubiks.cube.cube686)
 N_ACTIONS = 12
 
 _ARCHS = {   # reference model.py:17-21
@@ -33,6 +34,7 @@ _ARCHS = {   # reference model.py:17-21
     "fc_big": {"shared_sizes": [8192, 4096, 2048], "part_sizes": [1024, 512]},
     "res_small": {"shared_sizes": [4096, 1024], "part_sizes": [512], "res_blocks": 4, "res_size": 1024},
     "res_big": {"shared_sizes": [8192, 4096, 2048], "part_sizes": [1024, 512], "res_blocks": 6, "res_size": 2048},
+    "conv": {"shared_sizes": [4096, 2048], "part_sizes": [512], "conv_channels": [32, 64, 128], "cat_sizes": [2048]},
 }
 _ACTIVATIONS = {"elu": nn.ELU, "relu": nn.ReLU}
 
@@ -46,17 +48,24 @@ class ModelConfig:
         self.init = init
         self.is2024 = is2024
         self.id = hash(time())
-        if self.architecture == "conv":
-            raise NotImplementedError("the conv architecture needs the 6x8x6 representation (out of scope on MI355X)")
         if self.architecture not in _ARCHS:
             raise KeyError(f"Network architecture should be one of {sorted(_ARCHS)}, but '{architecture}' was given")
-        if not is2024:
-            raise NotImplementedError("only the 20x24 representation is implemented on MI355X")
+        if self.architecture == "conv" and is2024:
+            # the reference refuses the pair when a job is built (jobs.py:100): the convolutions run over the 8 stickers of a face
+            raise ValueError("the conv architecture reads the 6x8x6 representation (its convolutions run around the 8 stickers of each "
+                             "face): create it with ModelConfig(architecture='conv', is2024=False)")
         arch = _ARCHS[self.architecture]
         self.shared_sizes = list(arch["shared_sizes"])
         self.part_sizes = list(arch["part_sizes"])
         if self.architecture.startswith("res"):
             self.res_blocks, self.res_size = arch["res_blocks"], arch["res_size"]
+        if self.architecture == "conv":
+            self.conv_channels, self.cat_sizes = list(arch["conv_channels"]), list(arch["cat_sizes"])
+
+    @property
+    def input_width(self) -> int:
+        """Width of the one-hot network input: 480 (20x24) or 288 (6x8x6), reference cube.py:139-140."""
+        return OH_WIDTH if self.is2024 else OH_WIDTH_686
 
     def as_json_dict(self):
         name = [k for k, cls in _ACTIVATIONS.items() if isinstance(self.activation_function, cls)][0]
@@ -92,16 +101,20 @@ class NonConvResBlock(nn.Module):
 
 
 class Model(nn.Module):
-    """Shared trunk 480 -> shared_sizes, then a policy head (12 logits) and a value head (1)."""
+    """Shared trunk 480 (or 288 with config.is2024 == False) -> shared_sizes, then a policy head (12 logits) and a value head (1)."""
 
     def __init__(self, config: ModelConfig, logger=NullLogger()):
         super().__init__()
         self.config, self.log = config, logger
-        trunk_out = config.shared_sizes[-1]
+        self._construct_net()
+
+    def _construct_net(self, pv_input_size: int = None):
+        config = self.config
+        trunk_out = config.shared_sizes[-1] if pv_input_size is None else pv_input_size
         # Construction order = the reference's (model.py:117-129, 256-264): trunk, policy head, value head, THEN the residual
         # blocks appended to the trunk -- the order in which the initialisers draw from torch's generator, so that a seeded
         # `Model.create` has the reference's parameters bit for bit (tests/test_model.py, tests/golden/model_golden.npz).
-        self.shared_net = nn.Sequential(*self._stack([OH_WIDTH, *config.shared_sizes], last_is_output=False))
+        self.shared_net = nn.Sequential(*self._stack([config.input_width, *config.shared_sizes], last_is_output=False))
         self.policy_net = nn.Sequential(*self._stack([trunk_out, *config.part_sizes, N_ACTIONS], last_is_output=True))
         self.value_net = nn.Sequential(*self._stack([trunk_out, *config.part_sizes, 1], last_is_output=True))
         if config.architecture.startswith("res"):
@@ -112,7 +125,8 @@ class Model(nn.Module):
 
     @staticmethod
     def create(config: ModelConfig, logger=NullLogger()):
-        return Model(config, logger).to(gpu)
+        """The network `config` describes (reference model.py:105-115); the input width comes from config.is2024."""
+        return (ConvNet if config.architecture == "conv" else Model)(config, logger).to(gpu)
 
     def _stack(self, widths, last_is_output: bool):
         """Linear -> activation -> BatchNorm1d per hidden layer (model.py:143-161); a bare Linear at an output."""
@@ -169,6 +183,82 @@ class Model(nn.Module):
         model = Model.create(config, logger)
         model.load_state_dict(torch.load(path, map_location=gpu))
         return model.to(gpu)
+
+
+class _CircularPad(nn.Module):
+    """F.pad(x, padding, mode="circular") as a module (reference model.py:267-277): the 8 stickers of a face form a ring."""
+
+    def __init__(self, padding: list):
+        super().__init__()
+        self.padding = padding
+
+    def forward(self, x):
+        return F.pad(x, self.padding, mode="circular")
+
+
+def _conv1d_k3(x: torch.Tensor, conv: nn.Conv1d) -> torch.Tensor:
+    """conv(x) for the kernel-size-3, stride-1 convolutions of ConvNet as unfold + one GEMM over conv's own `weight` and `bias` (the
+    state_dict is the nn.Conv1d's).  The searches replay the network from a captured graph at many batch shapes; a plain GEMM is
+    captured like every other layer of the networks here, whereas the convolution library picks -- and on first sight of a shape
+    tunes -- an algorithm per shape."""
+    n, c, w = x.shape
+    assert conv.kernel_size == (3,) and conv.stride == (1,) and conv.padding == (0,) and conv.dilation == (1,) and conv.groups == 1
+    cols = x.unfold(2, 3, 1).permute(0, 2, 1, 3).reshape(n * (w - 2), c * 3)
+    y = torch.addmm(conv.bias, cols, conv.weight.reshape(conv.out_channels, c * 3).t())
+    return y.reshape(n, w - 2, conv.out_channels).permute(0, 2, 1)
+
+
+class ConvNet(Model):
+    """
+    The reference's convolutional network (model.py:279-338), 6x8x6 only:
+        x -> fc layers (shared_net) ------------------------------------+               +-> policy_net
+                                                                        +-> cat_net ->--+
+        x -> correctness (n,6,8) -> circular convs (shared_conv_net) ---+               +-> value_net
+    Module names and layer order are the reference's, so its state_dict loads with strict=True.
+    """
+
+    def _construct_net(self):
+        config = self.config
+        channels = [6, *config.conv_channels]
+        cat_input = channels[-1] * 8 + config.shared_sizes[-1]
+        conv = [_CircularPad([1, 1]), nn.Conv1d(channels[0], channels[1], kernel_size=3, stride=1)]   # no activation behind the first (model.py:294-296)
+        if config.batchnorm:
+            conv.append(nn.BatchNorm1d(channels[1]))
+        for c_in, c_out in zip(channels[1:-1], channels[2:]):
+            conv += [_CircularPad([1, 1]), nn.Conv1d(c_in, c_out, 3), config.activation_function]
+            if config.batchnorm:
+                conv.append(nn.BatchNorm1d(c_out))
+        self.shared_conv_net = nn.Sequential(*conv)
+        cat, sizes = [], [cat_input, *config.cat_sizes]
+        for w_in, w_out in zip(sizes[:-1], sizes[1:]):
+            cat += [nn.Linear(w_in, w_out), config.activation_function]
+            if config.batchnorm:
+                cat.append(nn.BatchNorm1d(w_out))
+        self.cat_net = nn.Sequential(*cat)
+        super()._construct_net(sizes[-1])   # trunk and heads behind the conv modules, as the reference registers them
+
+    def forward(self, x, policy=True, value=True):
+        assert policy or value
+        from librubiks.cube import cube686
+        fc_out = self.shared_net(x)
+        # rc686_as_correct_oh_* on device tensors, the same expression in torch on the CPU (no gradient flows through the comparison)
+        y = cube686.as_correct(x)
+        for module in self.shared_conv_net:
+            y = _conv1d_k3(y, module) if isinstance(module, nn.Conv1d) else module(y)
+        conv_out = y.reshape(len(x), -1)
+        x = self.cat_net(torch.cat([fc_out, conv_out], dim=1))
+        out = []
+        if policy:
+            out.append(self.policy_net(x))
+        if value:
+            out.append(self.value_net(x))
+        return out if len(out) > 1 else out[0]
+
+
+def _is_2024_fc_res(net) -> bool:
+    """Networks the folded engines (InferenceNet, SplitF32Net) take: fc_* / res_* on the 480-wide input.  A 6x8x6 first layer would
+    be a sum of 48 weight rows per state, which those engines' input kernels do not do."""
+    return isinstance(net, Model) and net.config.architecture.split("_")[0] in ("fc", "res") and net.config.is2024
 
 
 # =================================================================================================
@@ -251,7 +341,7 @@ class InferenceNet:
     """
 
     def __init__(self, model: Model, dtype=torch.bfloat16, device=None, first_layer_table: str = "auto"):
-        assert isinstance(model, Model) and model.config.architecture.split("_")[0] in ("fc", "res")
+        assert _is_2024_fc_res(model), "InferenceNet folds fc_* / res_* networks of the 20x24 representation"
         device = device or next(model.parameters()).device
         was_training = model.training
         model.eval()
@@ -828,13 +918,17 @@ def _activate_(x: torch.Tensor, act: nn.Module) -> torch.Tensor:
 
 
 class GenericNet:
-    """Calls an arbitrary torch module with the reference's convention net(oh) -> [policy, value]."""
+    """Calls an arbitrary torch module with the reference's convention net(oh) -> [policy, value].  `encoding` / `input_width` tell
+    the agents which one-hot the module reads (librubiks.cube.device.encode): "686" and 288 for a `Model` with config.is2024 ==
+    False -- every such network, the conv architecture among them, is served live through this engine."""
 
     input_dtype = torch.float32
 
     def __init__(self, module: nn.Module):
         self.module = module
         self.flops_per_state = None
+        is2024 = bool(getattr(getattr(module, "config", None), "is2024", True))
+        self.encoding, self.input_width = ("2024", OH_WIDTH) if is2024 else ("686", OH_WIDTH_686)
 
     @torch.no_grad()
     def __call__(self, oh: torch.Tensor):
@@ -855,7 +949,7 @@ def net_fingerprint(net, dtype=None):
     """
     if isinstance(net, (InferenceNet, SplitF32Net, GenericNet)):
         return (id(net),)
-    if isinstance(net, Model) and net.config.architecture.split("_")[0] in ("fc", "res"):
+    if _is_2024_fc_res(net):
         tensors = list(net.parameters()) + list(net.buffers())
         return (id(net), str(dtype)) + tuple((t.data_ptr(), t._version) for t in tensors)
     return (id(net), str(dtype))   # any other module is called live through GenericNet
@@ -865,7 +959,7 @@ def make_inference_net(net, dtype=torch.bfloat16):
     """The fastest engine that preserves `net`'s eval-mode function."""
     if isinstance(net, (InferenceNet, SplitF32Net, GenericNet)):
         return net
-    if isinstance(net, Model) and net.config.architecture.split("_")[0] in ("fc", "res"):
+    if _is_2024_fc_res(net):
         if dtype in (F32_SPLIT, F32_SPLIT_DET):
             try:
                 return SplitF32Net(net, deterministic=dtype == F32_SPLIT_DET)

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from librubiks import _hip, gpu, no_grad
-from librubiks.cube.device import DeviceCubes
+from librubiks.cube.device import DeviceCubes, encode
 from librubiks.model import F32_SPLIT, F32_SPLIT_DET, Model, net_fingerprint
 from librubiks.solving import astar_device as ad
 from librubiks.solving import bfs_device as bd
@@ -913,8 +913,7 @@ class AStar(DeepAgent):
         """lambda * G[indeces] - value_net(states) (agents.py:369-383), evaluated on the device net."""
         from librubiks.model import make_inference_net
         eng = self.batch.engine if self.batch is not None else make_inference_net(self._search_net(), self.net_dtype)
-        oh = DeviceCubes.from_numpy(np.asarray(states)).as_oh(eng.input_dtype)
-        h = -eng.value(oh).cpu().numpy().astype(np.float64)
+        h = -eng.value(encode(eng, DeviceCubes.from_numpy(np.asarray(states)))).cpu().numpy().astype(np.float64)
         return self.lambda_ * np.asarray(self.G)[indeces] + h
 
 
@@ -928,13 +927,13 @@ def _evaluate(engine, cubes: DeviceCubes):
     """(policy logits float32[n,12], values float32[n]) of device-resident states."""
     if getattr(engine, "supports_cubes", False):
         return engine.forward_cubes(cubes)
-    return engine(cubes.as_oh(engine.input_dtype))
+    return engine(encode(engine, cubes))
 
 
 def _values(engine, cubes: DeviceCubes):
     if getattr(engine, "supports_cubes", False):
         return engine.value_cubes(cubes)
-    return engine.value(cubes.as_oh(engine.input_dtype))
+    return engine.value(encode(engine, cubes))
 
 
 class _StepAgent(Agent):

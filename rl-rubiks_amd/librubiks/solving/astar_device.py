@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from librubiks import _hip
-from librubiks.cube.device import DeviceCubes
+from librubiks.cube.device import DeviceCubes, encode
 from librubiks.model import make_inference_net, net_fingerprint
 from librubiks.solving.mcts_device import unpack_keys
 from librubiks.solving.results import QueueTable
@@ -96,7 +96,7 @@ class AStarBatch:
             self._oh = None
             self._x1 = self.engine.workspace(rows)
         else:
-            self._oh = torch.empty((rows, 480), dtype=self.engine.input_dtype, device=self.device)
+            self._oh = torch.empty((rows, getattr(self.engine, "input_width", 480)), dtype=self.engine.input_dtype, device=self.device)
 
     def reset(self, roots: DeviceCubes):
         """Every problem b starts from roots[b] (roots may hold more scrambles: the rest wait for `plant`)."""
@@ -145,8 +145,6 @@ class AStarBatch:
 
     def _values_of_new(self, total: int):
         """Value head on the `total` compacted new states, chunked through the one-hot buffer."""
-        lib, st = self.lib, _hip.stream_ptr()
-        soa = self.new_states.soa
         if getattr(self.engine, "supports_cubes", False):   # input layer fused with the one-hot encoding: no (n, 480) matrix
             for lo in range(0, total, NET_CHUNK):
                 n = min(NET_CHUNK, total - lo)
@@ -154,11 +152,8 @@ class AStarBatch:
             return
         for lo in range(0, total, NET_CHUNK):
             n = min(NET_CHUNK, total - lo)
-            oh = self._oh[:n]
-            fn = lib.rc_as_oh_bf16 if oh.dtype == torch.bfloat16 else lib.rc_as_oh_f32
             # column offset lo is a multiple of 16, so the shifted plane pointer stays 16-byte aligned
-            _hip.check(fn(soa.data_ptr() + lo, oh.data_ptr(), n, self.new_states.stride, st), "rc_as_oh")
-            self.values[lo:lo + n] = self.engine.value(oh)
+            self.values[lo:lo + n] = self.engine.value(encode(self.engine, self.new_states, self._oh[:n], lo, n))
 
     def iteration(self, lambda_: float, max_states: int) -> int:
         """pop N, expand, dedup, evaluate the new states, push, win check, relax.  Returns #new states."""

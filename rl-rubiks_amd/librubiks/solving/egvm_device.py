@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from librubiks import _hip
-from librubiks.cube.device import DeviceCubes
+from librubiks.cube.device import DeviceCubes, encode
 from librubiks.model import SplitF32Net, _CubeWindow, make_inference_net, net_fingerprint
 from librubiks.solving.astar_device import NET_CHUNK
 
@@ -164,7 +164,7 @@ class EGVMBatch:
         self._fused = bool(getattr(self.engine, "supports_cubes", False))
         rows = min(NET_CHUNK, self.R)
         self._x1 = self.engine.workspace(rows) if self._fused else None
-        self._oh = None if self._fused else torch.empty((rows, 480), dtype=self.engine.input_dtype, device=self.device)
+        self._oh = None if self._fused else torch.empty((rows, getattr(self.engine, "input_width", 480)), dtype=self.engine.input_dtype, device=self.device)
         # the head of all rows where it does not come out of the engine as one tensor (several chunks, or logits and values apart)
         self._head_buf = None if self._fused and self.R <= NET_CHUNK else torch.zeros((self.R, 16), dtype=torch.float32, device=self.device)
         self._graphs, self._graph_pool = {}, None
@@ -179,10 +179,7 @@ class EGVMBatch:
             if isinstance(eng, SplitF32Net):
                 return eng._forward_cubes(rows, eng.layers, lo, n)
             return eng.head_cubes(_CubeWindow(rows.soa.data_ptr() + lo, n, rows.stride), x1)
-        oh = self._oh[:n]
-        fn = self.lib.rc_as_oh_bf16 if oh.dtype == torch.bfloat16 else self.lib.rc_as_oh_f32
-        _hip.check(fn(rows.soa.data_ptr() + lo, oh.data_ptr(), n, rows.stride, _hip.stream_ptr()), "rc_as_oh")
-        logits, values = eng(oh)
+        logits, values = eng(encode(eng, rows, self._oh[:n], lo, n))
         out = self._head_buf[lo:lo + n]
         out[:, :N_ACT].copy_(logits)
         out[:, N_ACT].copy_(values)

@@ -20,7 +20,7 @@ import torch
 
 from librubiks import _hip
 from librubiks._vmm import VmmArray, zeros_or_trim
-from librubiks.cube.device import DeviceCubes
+from librubiks.cube.device import DeviceCubes, encode
 from librubiks.model import make_inference_net, net_fingerprint
 
 RUNNING, SOLVED, EXHAUSTED, PATH_OVERFLOW, ROOT_SOLVED, CORRUPT = 0, 1, 2, 3, 4, 5
@@ -668,7 +668,7 @@ class MCTSForest:
             self._oh = None
             self._x1 = self.engine.workspace(ROWS * self.B)
         else:
-            self._oh = torch.empty((ROWS * self.B, 480), dtype=self.engine.input_dtype, device=self.device)
+            self._oh = torch.empty((ROWS * self.B, getattr(self.engine, "input_width", 480)), dtype=self.engine.input_dtype, device=self.device)
         self._graphs = {}
         self._graph_pool = None   # (a pool whose graphs have all been dropped cannot be captured into again: a fresh one next time)
 
@@ -685,7 +685,7 @@ class MCTSForest:
         if self._fused:
             logits, values = self.engine.forward_cubes(cubes, None if self._x1 is None else self._x1[:rows])
         else:
-            cubes.as_oh(out=self._oh[:rows])
+            encode(self.engine, cubes, self._oh[:rows])
             logits, values = self.engine(self._oh[:rows])
         torch.softmax(logits, dim=1, out=self.probs[:rows])   # agents.py:552 (`p.softmax(dim=1)`)
         self.values[:rows].copy_(values)

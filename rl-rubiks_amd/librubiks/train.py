@@ -17,8 +17,8 @@ import torch
 import torch.distributed as dist
 
 from librubiks import _hip, cube, gpu, no_grad
-from librubiks.cube.device import DeviceCubes
-from librubiks.model import Model, make_inference_net, net_fingerprint
+from librubiks.cube.device import DeviceCubes, encode
+from librubiks.model import GenericNet, Model, make_inference_net, net_fingerprint
 from librubiks.utils import NullLogger, TickTock
 
 _FIX = {"paper": 0, "reward0": 0, "lapanfix": 1, "schultzfix": 2}
@@ -206,6 +206,7 @@ class Train:
         kid_solved, state_solved = kid_solved.view(torch.uint8), state_solved.view(torch.uint8)
         values = torch.empty(12 * n, dtype=torch.float32, device=states.soa.device)
         engine = self._adi_engine(net)
+        live = GenericNet(net)   # the torch module itself, with the one-hot its config asks for (480 wide, or 288 for is2024 = False)
         for lo in range(0, 12 * n, self.adi_chunk):   # chunked like the reference's adi_ff_batches (train.py:301-310)
             m = min(self.adi_chunk, 12 * n - lo)
             if engine is not None and engine.supports_cubes and lo % 16 == 0:
@@ -215,7 +216,7 @@ class Train:
             if engine is not None and engine.supports_cubes:
                 values[lo:lo + m] = engine.value_cubes(part)
             else:
-                values[lo:lo + m] = net(part.as_oh(torch.float32), policy=False, value=True).float().reshape(-1)
+                values[lo:lo + m] = live.value(encode(live, part))
         policy_targets = torch.empty(n, dtype=torch.int64, device=values.device)
         value_targets = torch.empty(n, dtype=torch.float32, device=values.device)
         _hip.check(lib.rc_adi_targets(values.data_ptr(), kid_solved.data_ptr(), state_solved.data_ptr(), n, D,
@@ -225,7 +226,7 @@ class Train:
         weighted = np.tile(1 / np.arange(1, D + 1), G)
         ws, us = weighted.sum(), len(weighted)
         loss_weights = ((1 - alpha) * weighted / ws + alpha * np.ones_like(weighted) / us) * (ws + us)
-        return states.as_oh(torch.float32), policy_targets, value_targets, \
+        return encode(live, states), policy_targets, value_targets, \
             torch.from_numpy(loss_weights).float().to(values.device)
 
     _engine_cache = None
@@ -235,7 +236,7 @@ class Train:
         reference's arithmetic and the default), or one of the inference engines -- F32_SPLIT: fp32 accuracy on the f16 matrix
         cores, torch.bfloat16: the fast engine -- straight from the device-resident substates (no one-hot matrix).  Rebuilt when
         the generator's weights change (`net_fingerprint`)."""
-        if self.adi_net_dtype == torch.float32 or not (isinstance(net, Model) and net.config.architecture.startswith("fc")):
+        if self.adi_net_dtype == torch.float32 or not (isinstance(net, Model) and net.config.architecture.startswith("fc") and net.config.is2024):
             return None
         fp = net_fingerprint(net, self.adi_net_dtype)
         if self._engine_cache is None or self._engine_cache[0] != fp:
