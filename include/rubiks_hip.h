@@ -769,6 +769,27 @@ int rc_as_correct_from2024_f32(const int8_t *soa, float *out, size_t n, size_t s
 int rc686_as_correct_oh_f32(const float *oh, float *out, size_t n, rc_stream_t stream);
 int rc686_as_correct_oh_bf16(const uint16_t *oh, uint16_t *out, size_t n, rc_stream_t stream);
 
+/* The conv branch of ConvNet (reference librubiks/model.py:279-338: `shared_conv_net` built at :290-303, run at :326-329 on
+ * cube.as_correct(x), cube.py:372-380) from the 20 code planes, one launch (csrc/rubiks_conv686.hip):
+ *     out[i][col0 + c * 8 + p] = act(conv3(pad(act(conv2(pad(conv1(pad(as_correct(state i)))))))))[c][p],   c < 128, p < 8
+ * -- kernel-size-3 convolutions, circular over the 8 stickers of a face, channels 6 -> 32 -> 64 -> 128, no activation behind the
+ * first (model.py:294-296), flattened (channel, position) as `conv_out.reshape(len(x), -1)` does (:329).  The BatchNorms are the
+ * caller's business: folded into the weights (librubiks/model.py `_fold_conv`).  fp32 multiply-adds in a fixed order per output,
+ * whatever n, the window (soa + lo, lo % 16 == 0) or the launch: bit-reproducible per state.
+ *   weights  31 296 floats, 16-byte aligned: layer l (c_in -> c_out, G = c_out / 16) at offset 0 / 576 / 6 720 as
+ *            [c_in][16][3 taps][G]: element ((c * 16 + o / G) * 3 + t) * G + o % G = W_l[o][c][t] of nn.Conv1d's weight
+ *   biases   224 floats: b_1 (32), b_2 (64), b_3 (128)
+ *   out      row pitch `out_pitch` and first column `col0` in ELEMENTS of the format (both multiples of 8), out 16-byte aligned:
+ *            out_format 0: float;  1: bf16;  2: IEEE half [hi | lo] with y = hi + lo 2^-11, a row being out_pitch halves, the hi
+ *            block at column col0, the lo block at column out_pitch / 2 + col0.  Columns outside the block are not touched.
+ *   range_flag (may be NULL): formats 1 and 2 OR 1 into it when an output is not finite, format 2 also beyond +-65 504.
+ * rc_conv686_packed_floats: the sizes of the two packed arrays for conv_channels (c1, c2, c3); RC_ERR_RANGE for any other than
+ * the reference's (32, 64, 128) (model.py:21), which is all the kernel is built for. */
+int rc_conv686_packed_floats(int c1, int c2, int c3, size_t *n_weights, size_t *n_biases);
+int rc_conv686_branch(const int8_t *soa, size_t n, size_t stride, const float *weights, const float *biases, void *out,
+                      size_t out_pitch, size_t col0, int out_format, int activation, float alpha, int32_t *range_flag,
+                      rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,9 @@ SIGNATURES = {
     "rc_as_correct_from2024_f32": [P, P, SZ, SZ, P],
     "rc686_as_correct_oh_f32": [P, P, SZ, P],
     "rc686_as_correct_oh_bf16": [P, P, SZ, P],
+    # the conv branch of the 6x8x6 ConvNet from the code planes (csrc/rubiks_conv686.hip)
+    "rc_conv686_packed_floats": [I, I, I, P, P],
+    "rc_conv686_branch": [P, SZ, SZ, P, P, P, SZ, SZ, I, I, ctypes.c_float, P, P],
 }
 _RESTYPES = {"rc_error_string": c_char_p, "rc_split_layer_struct_bytes": c_size_t}
 

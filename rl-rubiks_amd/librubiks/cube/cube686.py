@@ -101,6 +101,31 @@ def to2024(states686: np.ndarray) -> np.ndarray:
     return out[0] if single else out
 
 
+_torch_tables = {}
+
+
+def codes_from_oh(oh: torch.Tensor, check: bool = True) -> torch.Tensor:
+    """(n,288) one-hot tensor -> (n,20) int8 codes on the same device: `to2024` in torch (the bridge inverted by table lookups, no
+    host round trip; safe inside a graph capture with check=False).  check: raise ValueError unless every row is a cube state."""
+    assert oh.dim() == 2 and oh.shape[1] == OH_WIDTH_686, f"expected (n,288), got {tuple(oh.shape)}"
+    tabs = _torch_tables.get(oh.device)
+    if tabs is None:
+        _, _, pos_stickers, inverse = _host_tables()
+        q = np.arange(20)
+        tabs = _torch_tables[oh.device] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(oh.device) for a in (
+            pos_stickers, inverse, (q < 8).astype(np.int64), np.where(q < 8, 3 * q, 2 * (q - 8)), q))
+    pos_stickers, inverse, corner, base, q = tabs
+    col = oh.reshape(len(oh), 48, 6).argmax(2)
+    c = col[:, pos_stickers]                                          # (n, 20 positions, 3 stickers)
+    who = inverse[q[None, :], c[..., 0] * 36 + c[..., 1] * 6 + c[..., 2] * corner]   # (n, 20, 2): cubie, orientation
+    if check and not bool((who[..., 0].sort(1).values == q).all()):
+        raise ValueError("not a batch of 6x8x6 one-hot cube states (a position shows colours no cubie has, or a cubie sits twice): "
+                         "evaluate device states with the engine's forward_cubes / head_cubes / value_cubes instead")
+    codes = torch.zeros((len(oh), 20), dtype=torch.int64, device=oh.device)
+    codes.scatter_(1, who[..., 0].clamp_min(0), base[None, :] + who[..., 1])
+    return codes.to(torch.int8)
+
+
 ###########################
 # Staging for small calls
 ###########################

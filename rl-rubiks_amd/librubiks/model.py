@@ -256,9 +256,148 @@ class ConvNet(Model):
 
 
 def _is_2024_fc_res(net) -> bool:
-    """Networks the folded engines (InferenceNet, SplitF32Net) take: fc_* / res_* on the 480-wide input.  A 6x8x6 first layer would
-    be a sum of 48 weight rows per state, which those engines' input kernels do not do."""
+    """Networks that go to the folded engines (InferenceNet, SplitF32Net) when handed over bare: fc_* / res_* on the 480-wide input.
+    6x8x6 networks are served live unless the caller asks for the engines with `Folded(net)`."""
     return isinstance(net, Model) and net.config.architecture.split("_")[0] in ("fc", "res") and net.config.is2024
+
+
+CONV_CHANNELS = [6, 32, 64, 128]   # what rc_conv686_branch is built for: the reference's conv_channels behind the 6 faces (model.py:21)
+
+
+def _not_foldable(net):
+    """None if the folded engines take `net`, else what stands in the way (a sentence for an error message)."""
+    if not isinstance(net, Model):
+        return f"{type(net).__name__} is not a librubiks Model (fc_* / res_* / conv)"
+    arch = net.config.architecture
+    if arch == "conv":
+        if net.config.is2024:
+            return "the conv architecture reads the 6x8x6 representation"
+        if [6, *net.config.conv_channels] != CONV_CHANNELS:
+            return f"conv_channels {net.config.conv_channels}: the conv-branch kernel (rc_conv686_branch) is built for {CONV_CHANNELS[1:]} only"
+        return None
+    if arch.split("_")[0] not in ("fc", "res"):
+        return f"architecture {arch!r} has no folded form"
+    return None
+
+
+class Folded:
+    """`Folded(net)` in place of `net` asks the agents, `Evaluator` and the forests for the folded engines (SplitF32Net /
+    InferenceNet, by `net_dtype`) of a 6x8x6 `Model` / `ConvNet`, which they serve through the live module when it is handed over
+    bare.  A plain handle: `make_inference_net` and `net_fingerprint` look through it, nothing else is asked of a `net`.  Around a
+    20x24 network it changes nothing."""
+
+    def __init__(self, net):
+        reason = _not_foldable(net)
+        if reason is not None:
+            raise ValueError(f"Folded: {reason}")
+        self.net = net
+
+
+def _bridge_matrix() -> torch.Tensor:
+    """float64 [288][480], 0 / 1: column 24 j + v has the ones of the 6x8x6 one-hot that cubie j with code v sets -- entries
+    sticker * 6 + colour of its 3 (corner) or 2 (edge) pairs in cube686.get_bridge_table(); sticker 255 = no such pair."""
+    from librubiks.cube import cube686
+    bridge = cube686.get_bridge_table().astype("int64")
+    B = torch.zeros((OH_WIDTH_686, OH_WIDTH), dtype=torch.float64)
+    for j in range(20):
+        for v in range(24):
+            for sticker, colour in bridge[j, v]:
+                if sticker != 255:
+                    B[sticker * 6 + colour, 24 * j + v] = 1.0
+    return B
+
+
+def _fold_bridge(W1: torch.Tensor) -> torch.Tensor:
+    """W1 [H][288] of a 6x8x6 input layer -> float64 [H][480] with W1 @ oh288(state) == folded @ oh480(state) for every cube state:
+    a legal cube's 288-wide one-hot is a fixed function of its 20 codes, so row 24 j + v of the folded table is the sum of the 3 or 2
+    columns of W1 that cubie j with code v selects, and the fused input kernels of the 20x24 networks (sum of 20 table rows per state)
+    serve the 6x8x6 ones."""
+    assert W1.shape[1] == OH_WIDTH_686, tuple(W1.shape)
+    return W1.double() @ _bridge_matrix().to(W1.device)
+
+
+def _fold_conv(seq: nn.Sequential):
+    """[(W [c_out][c_in][3], b)] in float64 of ConvNet.shared_conv_net in eval mode, each BatchNorm folded into the NEXT convolution
+    -- a per-channel affine commutes with circular padding: the scale goes onto the c_in columns, the shift through the three taps
+    into the bias -- and the last BatchNorm's (scale, shift) per channel (or None) for the Linear that reads the flattened output."""
+    out, carry = [], None
+    for m in seq:
+        if isinstance(m, nn.Conv1d):
+            assert m.kernel_size == (3,) and m.stride == (1,) and m.padding == (0,) and m.dilation == (1,) and m.groups == 1
+            W, b = m.weight.double(), m.bias.double()
+            if carry is not None:
+                scale, shift = carry
+                b = b + (W * shift[None, :, None]).sum((1, 2))
+                W = W * scale[None, :, None]
+                carry = None
+            out.append((W, b))
+        elif isinstance(m, nn.BatchNorm1d):
+            carry = _bn_affine(m)
+        else:
+            assert isinstance(m, (_CircularPad, nn.ELU, nn.ReLU)), f"cannot fold {type(m).__name__}"
+    return out, carry
+
+
+def _conv_branch_torch(x: torch.Tensor, convs, act) -> torch.Tensor:
+    """The folded conv branch as a torch expression: x (n,6,8) correctness map -> (n, 1024), flattened (channel, position).  The CPU /
+    float64 engine, and what rc_conv686_branch is tested against."""
+    for i, (W, b) in enumerate(convs):
+        x = b[None, :, None] + sum(torch.einsum("oc,ncp->nop", W[:, :, t], torch.roll(x, 1 - t, 2)) for t in range(3))
+        if i and act is not None:   # no activation behind the first convolution (reference model.py:294-296)
+            x = F.relu(x) if isinstance(act, nn.ReLU) else F.elu(x, alpha=act.alpha)
+    return x.reshape(len(x), -1)
+
+
+def pack_conv686(convs):
+    """The float32 (weights, biases) arrays of rc_conv686_branch from the three folded layers (layout: include/rubiks_hip.h)."""
+    ws = []
+    for W, _ in convs:
+        c_out, c_in, _ = W.shape
+        ws.append(W.reshape(16, c_out // 16, c_in, 3).permute(2, 0, 3, 1).reshape(-1))
+    return torch.cat(ws).float().contiguous(), torch.cat([b for _, b in convs]).float().contiguous()
+
+
+class _ConvBranch:
+    """The folded conv branch of one engine: float64 layers, their copy in the engine's dtype for the torch expression, the packed
+    float32 arrays of the kernel."""
+
+    def __init__(self, convs, act, device, dtype):
+        from librubiks import _hip
+        nw, nb = ctypes.c_size_t(), ctypes.c_size_t()
+        rc = _hip.load().rc_conv686_packed_floats(*[W.shape[0] for W, _ in convs], ctypes.byref(nw), ctypes.byref(nb))
+        if rc != 0 or [convs[0][0].shape[1]] + [W.shape[0] for W, _ in convs] != CONV_CHANNELS:
+            raise ValueError(f"conv branch {[W.shape[0] for W, _ in convs]}: rc_conv686_branch is built for {CONV_CHANNELS[1:]} only")
+        self.convs64, self.act = convs, act
+        self.convs = [(W.to(device=device, dtype=dtype), b.to(device=device, dtype=dtype)) for W, b in convs]
+        w, b = pack_conv686(convs)
+        assert w.numel() == nw.value and b.numel() == nb.value
+        self.weights, self.biases = w.to(device), b.to(device)
+        self.code = 0 if act is None else 1 if isinstance(act, nn.ReLU) else 2
+        self.alpha = float(getattr(act, "alpha", 1.0))
+        self.width = convs[-1][0].shape[0] * 8
+
+    def torch_from_oh(self, oh: torch.Tensor, dtype) -> torch.Tensor:
+        from librubiks.cube import cube686
+        x = cube686.as_correct(oh.detach())
+        return _conv_branch_torch(x.to(dtype), self.convs, self.act)
+
+    def launch(self, cubes, out: torch.Tensor, col0: int, fmt: int, range_flag=None):
+        """rc_conv686_branch of `cubes` (DeviceCubes or _CubeWindow) into columns col0 .. of `out` (fmt 2: of both halves)."""
+        from librubiks import _hip
+        assert out.is_contiguous() and out.shape[0] == cubes.n
+        _hip.check(_hip.lib().rc_conv686_branch(_soa_ptr(cubes), cubes.n, cubes.stride, self.weights.data_ptr(), self.biases.data_ptr(),
+                                                out.data_ptr(), out.shape[1], col0, fmt, self.code, self.alpha, _ptr(range_flag),
+                                                _hip.stream_ptr()), "rc_conv686_branch")
+        return out
+
+
+def _cubes_from_oh686(oh: torch.Tensor):
+    """The states a 288-wide one-hot batch encodes, as device cubes (cube686.codes_from_oh: the bridge inverted in torch).  Checked
+    unless a graph is being captured (the check reads a flag back)."""
+    from librubiks.cube import cube686
+    from librubiks.cube.device import DeviceCubes
+    check = not (oh.is_cuda and torch.cuda.is_current_stream_capturing())
+    return DeviceCubes.from_aos(cube686.codes_from_oh(oh, check=check).contiguous())
 
 
 # =================================================================================================
@@ -273,11 +412,12 @@ class LayerOpts:
     """What a folded layer does besides y = act(W x + b): `save` = its input is the skip connection of a residual block,
     `add` = that input is added in front of the activation (reference model.py:221-247: activate(bn2(layer2(.)) + x)),
     `post` = (scale, shift) of an eval-mode BatchNorm BEHIND the activation that could not be folded into the next Linear
-    because a skip connection reads its output as well."""
-    __slots__ = ("save", "add", "post")
+    because a skip connection reads its output as well, `cat` = this layer's input is the previous output concatenated with the conv
+    branch of the same cubes (ConvNet's cat_net, reference model.py:329-330)."""
+    __slots__ = ("save", "add", "post", "cat")
 
-    def __init__(self, save=False, add=False, post=None):
-        self.save, self.add, self.post = save, add, post
+    def __init__(self, save=False, add=False, post=None, cat=False):
+        self.save, self.add, self.post, self.cat = save, add, post, cat
 
 
 def _fold_stack(seq: nn.Sequential, carry=None):
@@ -297,7 +437,7 @@ def _fold_stack(seq: nn.Sequential, carry=None):
         if isinstance(lin, NonConvResBlock):
             if carry is not None:   # the block's input feeds a Linear AND the skip: the BatchNorm in front of it is applied for real
                 assert out, "a residual block cannot open the network behind a BatchNorm"
-                opts[-1] = LayerOpts(opts[-1].save, opts[-1].add, (carry[0], carry[1]))
+                opts[-1] = LayerOpts(opts[-1].save, opts[-1].add, (carry[0], carry[1]), opts[-1].cat)
                 carry = None
             for j, (layer, bn) in enumerate(((lin.layer1, getattr(lin, "batchnorm1", None)), (lin.layer2, getattr(lin, "batchnorm2", None)))):
                 W, b = layer.weight.double(), layer.bias.double()
@@ -336,17 +476,44 @@ class InferenceNet:
     """
     Eval-mode forward of an fc_* `Model` as a chain of fused GEMMs:
         x -> [Linear+act]* (trunk) -> [Linear+act] (both heads' first layers side by side) -> ... -> [13 outputs]
-    Returns (policy logits float32[n,12], values float32[n]).  Any other torch module (ResNet models,
-    test stand-ins) goes through `GenericNet`, which simply calls it.
+    Returns (policy logits float32[n,12], values float32[n]).  Any other torch module (test stand-ins) goes through
+    `GenericNet`, which simply calls it.
+    Networks of the 6x8x6 representation (config.is2024 == False) are taken as well: the input layer reaches the fused kernel as
+    its 480-row bridge fold (`_fold_bridge`), and the conv architecture becomes the same kind of layer list with one layer --
+    cat_net's first -- whose input is [trunk output | conv branch of the same cubes] (LayerOpts.cat; rc_conv686_branch from the
+    cube states, a torch expression of the same folded weights on the CPU / in float64).  Such engines carry encoding = "686".
     """
 
     def __init__(self, model: Model, dtype=torch.bfloat16, device=None, first_layer_table: str = "auto"):
-        assert _is_2024_fc_res(model), "InferenceNet folds fc_* / res_* networks of the 20x24 representation"
+        reason = _not_foldable(model)
+        if reason is not None:
+            raise ValueError(f"InferenceNet folds fc_* / res_* networks of either representation and the 6x8x6 conv network: {reason}")
         device = device or next(model.parameters()).device
+        is686 = not model.config.is2024
+        # which one-hot the one-hot entry points read (librubiks.cube.device.encode follows these where supports_cubes is false)
+        self.encoding, self.input_width = ("686", OH_WIDTH_686) if is686 else ("2024", OH_WIDTH)
+        self._conv = None
         was_training = model.training
         model.eval()
         with torch.no_grad():
             trunk, carry = _fold_stack(model.shared_net)
+            if model.config.architecture == "conv":
+                # [fc trunk | conv branch] -> cat_net: the trunk's trailing BatchNorm and the last conv BatchNorm fold into the matching
+                # column blocks of cat_net[0] (torch.cat([fc_out, conv_out], 1): shared_sizes[-1] + 128 x 8 columns, conv_out flattened
+                # (channel, position)); cat_net's own BatchNorm is the carry into the heads
+                convs, conv_carry = _fold_conv(model.shared_conv_net)
+                self._conv = _ConvBranch(convs, model.config.activation_function, device, dtype)
+                w_fc = model.config.shared_sizes[-1]
+                if carry is not None or conv_carry is not None:
+                    at = convs[0][0].device
+                    one, zero = torch.ones(w_fc, dtype=torch.float64, device=at), torch.zeros(w_fc, dtype=torch.float64, device=at)
+                    fc = carry if carry is not None else (one, zero)
+                    cv = conv_carry if conv_carry is not None else (one[:1].expand(convs[-1][0].shape[0]), zero[:1].expand(convs[-1][0].shape[0]))
+                    carry = (torch.cat([fc[0], cv[0].repeat_interleave(8)]), torch.cat([fc[1], cv[1].repeat_interleave(8)]))
+                cat, carry = _fold_stack(model.cat_net, carry)
+                cat.opts[0] = LayerOpts(cat=True)
+                trunk.extend(cat)
+                trunk.opts.extend(cat.opts)
             pol, pc = _fold_stack(model.policy_net, carry)
             val, vc = _fold_stack(model.value_net, carry)
             assert pc is None and vc is None and len(pol) == len(val)
@@ -368,22 +535,29 @@ class InferenceNet:
             self._opts = {}
             for ls, os_ in ((self.layers, opts), (self.value_layers, list(trunk.opts) + [LayerOpts()] * len(val))):
                 for layer, o in zip(ls, os_):
-                    post = None if o.post is None else tuple(t.to(device=device, dtype=torch.float32).contiguous() for t in o.post)
-                    self._opts[id(layer)] = LayerOpts(o.save, o.add, post)
+                    post_dtype = torch.float64 if dtype == torch.float64 else torch.float32   # (the kernels read fp32; the float64 engine keeps the affine exact)
+                    post = None if o.post is None else tuple(t.to(device=device, dtype=post_dtype).contiguous() for t in o.post)
+                    self._opts[id(layer)] = LayerOpts(o.save, o.add, post, o.cat)
             self.residual = any(o.save for o in opts)
         model.train(was_training)
         self.dtype, self.device = dtype, device
         self.flops_per_state = 2 * sum(W.shape[0] * W.shape[1] for W, _, _ in self.layers)
+        if self._conv is not None:
+            self.flops_per_state += 2 * 8 * sum(W.numel() for W, _ in self._conv.convs64)
         # Input layer fused with the one-hot encoding on the matrix cores (csrc/rubiks_net.hip): needs bf16 and H % 128 == 0.
         # The Linear weight as stored, in IEEE half when every weight fits its range (11 mantissa bits, closer to fp32 than bf16;
         # v_mfma_f32_32x32x16_f16), in bf16 otherwise (checkpoints without BatchNorm / with `he` init / early in training).
         W1, b1, act1 = self.layers[0]
         self._fused_first = None
         assert first_layer_table in ("auto", "onehot"), first_layer_table
-        if dtype == torch.bfloat16 and W1.is_cuda and W1.shape[0] % 128 == 0 and W1.shape[1] == OH_WIDTH \
+        # A 6x8x6 input layer reaches the fused kernels as its 480-row bridge fold (`_fold_bridge`); the 288-wide matrix stays in
+        # `layers` for the one-hot entry points.
+        if dtype == torch.bfloat16 and W1.is_cuda and W1.shape[0] % 128 == 0 and W1.shape[1] == self.input_width \
                 and first_layer_table != "onehot":
             code = 0 if act1 is None else 1 if isinstance(act1, nn.ReLU) else 2
             W1_full = layers[0][0].to(device)
+            if is686:
+                W1_full = _fold_bridge(W1_full)
             half_ok = bool(torch.isfinite(W1_full).all()) and float(W1_full.abs().max()) < 3.0e4
             table = W1_full.to(torch.float16 if half_ok else torch.bfloat16).contiguous()
             self._fused_first = (table, layers[0][1].to(device).float().contiguous(), code,
@@ -395,7 +569,7 @@ class InferenceNet:
 
     @torch.no_grad()
     def __call__(self, oh: torch.Tensor):
-        out = self._run(self.layers, oh).float()
+        out = self._run(self.layers, oh, oh).float()
         return out[:, :N_ACTIONS], out[:, N_ACTIONS]
 
     @property
@@ -439,8 +613,8 @@ class InferenceNet:
         """
         x = self.first_layer(cubes, x1)
         if not self._fused_head_ok():
-            return self._run(self.layers[1:], x)
-        x = self._run(self.layers[1:-2], x)
+            return self._run(self.layers[1:], x, cubes)
+        x = self._run(self.layers[1:-2], x, cubes)
         W3, b3, _ = self.layers[-2]
         return self.head_from_raw(torch.addmm(b3, x, W3.t()))   # pre-activation of the last hidden layer
 
@@ -461,13 +635,13 @@ class InferenceNet:
     @torch.no_grad()
     def forward_cubes(self, cubes, x1: torch.Tensor = None):
         """(policy logits, values) straight from device-resident cube states."""
-        out = self._run(self.layers[1:], self.first_layer(cubes, x1)).float()
+        out = self._run(self.layers[1:], self.first_layer(cubes, x1), cubes).float()
         return out[:, :N_ACTIONS], out[:, N_ACTIONS]
 
     @torch.no_grad()
     def value_cubes(self, cubes, x1: torch.Tensor = None, lo: int = 0, n: int = None) -> torch.Tensor:
         """Value head only, float32[n], straight from device-resident cube states (optionally the window lo..lo+n)."""
-        return self._run(self.value_layers[1:], self.first_layer(cubes, x1, lo, n)).float().reshape(-1)
+        return self._run(self.value_layers[1:], self.first_layer(cubes, x1, lo, n), _window(cubes, lo, n)).float().reshape(-1)
 
     # bf16 hidden layers with an activation as one kernel (rc_gemm_layer_bf16: bias, skip connection, activation fused) where its
     # 352 x 256 tiles fill the chip: 0.168 ms against 0.195 ms for hipBLASLt + the activation pass at 11 264 x 4096 x 2048; narrower
@@ -475,11 +649,29 @@ class InferenceNet:
     # as it does for the library's own choice of tiles: a row's bf16 result is not bit-identical across batch shapes.)
     fused_hidden = True
 
-    def _run(self, layers, x):
+    def _with_conv(self, x: torch.Tensor, src) -> torch.Tensor:
+        """[x | conv branch of the states x was computed from]: the operand of cat_net's first layer.  src: the device cubes (or a
+        window of them), or the one-hot batch.  On the GPU the branch is rc_conv686_branch writing its block of the wide buffer in
+        place, and x takes ONE extra pass (the layer kernels have no output pitch); the CPU / float64 engine is the torch expression."""
+        conv = self._conv
+        if isinstance(src, torch.Tensor):
+            if not (src.is_cuda and x.dtype in (torch.float32, torch.bfloat16)):
+                return torch.cat([x, conv.torch_from_oh(src, x.dtype)], 1)
+            src = _cubes_from_oh686(src)
+        assert src is not None, "this layer reads the conv branch: the cube states (or the one-hot batch) must come along"
+        assert x.dtype in (torch.float32, torch.bfloat16), "from device cubes the conv branch is written in float32 or bf16"
+        buf = torch.empty((x.shape[0], x.shape[1] + conv.width), dtype=x.dtype, device=x.device)
+        conv.launch(src, buf, x.shape[1], 0 if x.dtype == torch.float32 else 1, getattr(self, "range_flag", None))
+        buf[:, :x.shape[1]].copy_(x)
+        return buf
+
+    def _run(self, layers, x, src=None):
         skip = None
         for layer in layers:
             W, b, act = layer
             o = self._opts.get(id(layer)) or _PLAIN
+            if o.cat:
+                x = self._with_conv(x, src)
             if o.save:
                 skip = x
             if (act is not None and self.fused_hidden and x.dtype == torch.bfloat16 and x.is_cuda and x.is_contiguous()
@@ -507,7 +699,7 @@ class InferenceNet:
     @torch.no_grad()
     def value(self, oh: torch.Tensor) -> torch.Tensor:
         """Value head only, float32[n]."""
-        return self._run(self.value_layers, oh).float().reshape(-1)
+        return self._run(self.value_layers, oh, oh).float().reshape(-1)
 
 
 _PLAIN = LayerOpts()
@@ -588,6 +780,7 @@ class SplitF32Net:
         if self.deterministic:
             self.dtype = F32_SPLIT_DET
         self.device = ref.device
+        self.encoding, self.input_width, self._conv = ref.encoding, ref.input_width, ref._conv
         self._opts = {}
         self.layers, self.value_layers = self._split(ref.layers, ref._opts), self._split(ref.value_layers, ref._opts)
         self.residual = ref.residual
@@ -658,13 +851,24 @@ class SplitF32Net:
             code = 0 if act is None else 1 if isinstance(act, nn.ReLU) else 2
             alpha = float(getattr(act, "alpha", 1.0))
             if i == 0:    # one-hot input: x_lo = 0, so y = oh W_hi^T + 2^-11 oh W_lo^T = [oh, oh 2^-11] [W_hi | W_lo]^T
-                out.append(("in", torch.cat([hi, lo], 1).contiguous(), b.float().contiguous(), code, alpha, hi.contiguous(), lo.contiguous(),
-                            W.t().float().contiguous()))   # ... and W^T [480][H] in fp32: the rows rc_first_layer_gather_f16 adds up
+                B = torch.cat([hi, lo], 1).contiguous()
+                if W.shape[1] == OH_WIDTH_686:
+                    # a 6x8x6 input layer: everything the kernels that start from the cube states read comes from the 480-row bridge fold
+                    # (the table rows, the hi / lo tables, the operand behind rc_oh_split_f16); B, 288 wide, serves the one-hot entry points
+                    W = _fold_bridge(W)
+                    if not (bool(torch.isfinite(W).all()) and float(W.abs().max()) < 3.0e4):
+                        raise SplitRangeError(f"layer 0: bridge-folded weights up to {float(W.abs().max()):.3g} do not fit IEEE half")
+                    hi = W.half()
+                    lo = ((W - hi.double()) * SPLIT_SCALE).half()
+                B_cubes = B if B.shape[1] == 2 * OH_WIDTH else torch.cat([hi, lo], 1).contiguous()
+                out.append(("in", B, b.float().contiguous(), code, alpha, hi.contiguous(), lo.contiguous(),
+                            W.t().float().contiguous(),   # ... and W^T [480][H] in fp32: the rows rc_first_layer_gather_f16 adds up
+                            B_cubes))
             else:
                 out.append(("hid", hi.contiguous(), torch.cat([lo, hi], 1).contiguous(), b.float().contiguous(), code, alpha,
                             torch.cat([lo, hi, hi], 1).contiguous()))   # [W_lo | W_hi | W_hi]: the operand of rc_split_gemm_f16
             o = ref_opts.get(id(ref_layer)) or _PLAIN
-            self._opts[id(out[-1])] = LayerOpts(o.save, o.add, None if o.post is None else tuple(t.float().contiguous() for t in o.post))
+            self._opts[id(out[-1])] = LayerOpts(o.save, o.add, None if o.post is None else tuple(t.float().contiguous() for t in o.post), o.cat)
         return out
 
     fused_hidden = True   # hidden layers as one kernel each (rc_split_gemm_f16) where its tile fills the chip
@@ -771,7 +975,7 @@ class SplitF32Net:
     def _first_from_cubes(self, cubes, layers, lo: int = 0, n: int = None):
         """[hi | lo] activations of the input layer straight from device cubes, or None if the fused kernel does not apply."""
         from librubiks import _hip
-        _, B, b, code, alpha, Wh, Wl, Wrows = layers[0]
+        _, B, b, code, alpha, Wh, Wl, Wrows = layers[0][:8]
         H = Wh.shape[0]
         if not self.fused_input or H % 64 or len(layers) < 3:
             return None
@@ -791,13 +995,28 @@ class SplitF32Net:
 
     def _forward_cubes(self, cubes, layers, lo: int = 0, n: int = None) -> torch.Tensor:
         a = self._first_from_cubes(cubes, layers, lo, n)
+        src = _window(cubes, lo, n) if self._conv is not None else None
         if a is None:
-            return self._forward(self._input_from_cubes(cubes, lo, n), layers)
-        return self._forward(a, layers, first=1)
+            return self._forward(self._input_from_cubes(cubes, lo, n), layers, src=src)
+        return self._forward(a, layers, first=1, src=src)
+
+    def _with_conv(self, a: torch.Tensor, src) -> torch.Tensor:
+        """[hi | lo] of [x | conv branch of the same states]: rc_conv686_branch writes its two blocks of the wide operand in place
+        (format 2, range flag as every split-format writer), the halves of x take one strided copy."""
+        if isinstance(src, torch.Tensor):
+            src = _cubes_from_oh686(src)
+        assert src is not None, "this layer reads the conv branch: the cube states (or the one-hot batch) must come along"
+        n, w = a.shape[0], a.shape[1] // 2
+        wide = w + self._conv.width
+        buf = torch.empty((n, 2 * wide), dtype=torch.float16, device=a.device)
+        self._conv.launch(src, buf, w, 2, self.range_flag)
+        buf.view(n, 2, wide)[:, :, :w].copy_(a.view(n, 2, w))
+        return buf
 
     @torch.no_grad()
-    def _forward(self, a: torch.Tensor, layers, first: int = 0) -> torch.Tensor:
-        """a: [n, 960] half operand of the input layer (or, with first = 1, its [hi | lo] output) -> fp32 [n, n_out]."""
+    def _forward(self, a: torch.Tensor, layers, first: int = 0, src=None) -> torch.Tensor:
+        """a: [n, 960] half operand of the input layer (or, with first = 1, its [hi | lo] output) -> fp32 [n, n_out].  src: the cube
+        states (or one-hot batch) behind `a`, for a network with a conv branch."""
         from librubiks import _hip
         skip = None
         for i, layer in enumerate(layers):
@@ -806,11 +1025,15 @@ class SplitF32Net:
             last_hidden = i == len(layers) - 2
             n = a.shape[0]
             o = self._opts.get(id(layer)) or _PLAIN
+            if o.cat:
+                a = self._with_conv(a, src)
             if o.save:
                 skip = a
             res, post = (skip if o.add else None), o.post
             if layer[0] == "in":
                 _, B, b, code, alpha = layer[:5]
+                if a.shape[1] != B.shape[1]:   # the 960-wide operand from the cube states under a 6x8x6 network: the bridge fold
+                    B = layer[8]
                 part = torch.empty((1, n, B.shape[0]), dtype=torch.float32, device=a.device)
                 _mm_f32(a, B.t(), part[0])
                 n_corr = 0
@@ -863,6 +1086,8 @@ class SplitF32Net:
         """The states a one-hot batch encodes (cube.py:265-277 backwards), as device cubes: deterministic mode runs the input layer
         on the fused kernel for this entry point as well (the library GEMM on the one-hot matrix chooses its kernel by batch shape)."""
         from librubiks.cube.device import DeviceCubes
+        if oh.shape[1] == OH_WIDTH_686:   # the bridge inverted in torch; not a cube state: ValueError naming the *_cubes methods
+            return _cubes_from_oh686(oh)
         codes = oh.reshape(oh.shape[0], 20, 24).argmax(2).to(torch.int8)
         return DeviceCubes.from_aos(codes.contiguous())
 
@@ -870,14 +1095,14 @@ class SplitF32Net:
     def __call__(self, oh: torch.Tensor):
         if self.deterministic:
             return self.forward_cubes(self._cubes_from_oh(oh))
-        out = self._forward(self._input_from_oh(oh), self.layers)
+        out = self._forward(self._input_from_oh(oh), self.layers, src=oh)
         return out[:, :N_ACTIONS], out[:, N_ACTIONS]
 
     @torch.no_grad()
     def value(self, oh: torch.Tensor) -> torch.Tensor:
         if self.deterministic:
             return self.value_cubes(self._cubes_from_oh(oh))
-        return self._forward(self._input_from_oh(oh), self.value_layers).reshape(-1)
+        return self._forward(self._input_from_oh(oh), self.value_layers, src=oh).reshape(-1)
 
     @torch.no_grad()
     def head_cubes(self, cubes, x1=None) -> torch.Tensor:
@@ -902,6 +1127,15 @@ class _CubeWindow:
         self.ptr, self.n, self.stride = ptr, n, stride
 
 
+def _window(cubes, lo: int = 0, n: int = None):
+    """Rows lo .. lo + n (lo % 16 == 0) of `cubes` for a fused kernel: `cubes` itself when that is all of it."""
+    if not lo and n is None:
+        return cubes
+    n = cubes.n - lo if n is None else n
+    assert lo % 16 == 0 and 0 <= lo and lo + n <= cubes.n
+    return _CubeWindow(_soa_ptr(cubes) + lo, n, cubes.stride)
+
+
 def _soa_ptr(cubes) -> int:
     return cubes.ptr if isinstance(cubes, _CubeWindow) else cubes.soa.data_ptr()
 
@@ -920,7 +1154,8 @@ def _activate_(x: torch.Tensor, act: nn.Module) -> torch.Tensor:
 class GenericNet:
     """Calls an arbitrary torch module with the reference's convention net(oh) -> [policy, value].  `encoding` / `input_width` tell
     the agents which one-hot the module reads (librubiks.cube.device.encode): "686" and 288 for a `Model` with config.is2024 ==
-    False -- every such network, the conv architecture among them, is served live through this engine."""
+    False -- such a network, the conv architecture among them, is served live through this engine when it is handed over bare, and
+    by the folded engines when it is wrapped in `Folded`."""
 
     input_dtype = torch.float32
 
@@ -949,6 +1184,10 @@ def net_fingerprint(net, dtype=None):
     """
     if isinstance(net, (InferenceNet, SplitF32Net, GenericNet)):
         return (id(net),)
+    if isinstance(net, Folded):   # the folded engines are frozen copies of the weights, whichever representation: rebuilt after a step
+        net = net.net
+        tensors = list(net.parameters()) + list(net.buffers())
+        return (id(net), str(dtype)) + tuple((t.data_ptr(), t._version) for t in tensors)
     if _is_2024_fc_res(net):
         tensors = list(net.parameters()) + list(net.buffers())
         return (id(net), str(dtype)) + tuple((t.data_ptr(), t._version) for t in tensors)
@@ -956,10 +1195,14 @@ def net_fingerprint(net, dtype=None):
 
 
 def make_inference_net(net, dtype=torch.bfloat16):
-    """The fastest engine that preserves `net`'s eval-mode function."""
+    """The fastest engine that preserves `net`'s eval-mode function.  A 6x8x6 network goes to the live module unless the caller
+    asks for the folded engines with `Folded(net)`."""
     if isinstance(net, (InferenceNet, SplitF32Net, GenericNet)):
         return net
-    if _is_2024_fc_res(net):
+    folded = isinstance(net, Folded)   # asks for the engines on a 6x8x6 network, which is served live when handed over bare
+    if folded:
+        net = net.net
+    if folded or _is_2024_fc_res(net):
         if dtype in (F32_SPLIT, F32_SPLIT_DET):
             try:
                 return SplitF32Net(net, deterministic=dtype == F32_SPLIT_DET)
