@@ -661,6 +661,75 @@ int rc_egvm_plant(const rc_egvm_t *e, const int32_t *slots, uint32_t n, const in
 int rc_egvm_draw(uint32_t *mt_keys, int32_t *mt_pos, uint32_t n_games, const int32_t *games, const int32_t *slots, uint32_t n,
                  double cdf0, uint32_t workers, uint32_t depth, uint8_t *table, size_t table_stride, size_t n_rows);
 
+/* ---- one-step rollout agents: S games advanced one move per launch, in lock step ------------------
+ *
+ * Replaces the per-move Python of librubiks/solving/agents.py:23-38 (Agent.search) with the `_step` of RandomSearch (:82-90),
+ * PolicySearch (:132-151) and ValueSearch (:154-169).  A move of every running game =
+ *     policy / random:  [network on the S rows of states_soa: 12 logits per row] -> rc_rollout_step_policy
+ *     value:            [network on the 12 S rows of kids_soa: one value per row] -> rc_rollout_step_value
+ * The random numbers are the host's (rc_rollout_draw: one byte or one double per game and move, from the game's own np.random
+ * stream), so any number of moves is queued without the host.  Device pointers; nothing needs initialising except through
+ * rc_rollout_plant.  kids_soa and kid_solved are needed by the value step (and by a plant with children) only.
+ */
+#define RC_ROLLOUT_RUNNING 0
+#define RC_ROLLOUT_SOLVED 1        /* the move reached the solved cube (agents.py:33-35) */
+#define RC_ROLLOUT_EXHAUSTED 2     /* max_steps moves made */
+#define RC_ROLLOUT_QUEUE_FULL 3    /* the move's byte does not fit the queue row: the move was not made */
+#define RC_ROLLOUT_ROOT_SOLVED 4   /* agents.py:29 */
+#define RC_ROLLOUT_BAD_POLICY 5    /* a NaN probability where the policy is sampled (np.random.choice raises there) */
+#define RC_ROLLOUT_POLICY 255      /* decision byte: ask the network; 0 .. 11: that action */
+
+typedef struct rc_rollout {
+    uint32_t n_slots;     /* S: games played at a time */
+    uint32_t queue_width; /* bytes per row of `queues` */
+    size_t stride;        /* bytes between the planes of states_soa; kids_soa has 12 stride: multiple of 16, >= round_up(S, 16) */
+    int8_t *states_soa;   /* [20][stride] current states = the policy network's input */
+    int8_t *kids_soa;     /* [20][12 stride] child row 12 g + k = action k on state g (rc_expand12 order) = the value network's input */
+    uint8_t *kid_solved;  /* [12 stride] multi_is_solved of the children (agents.py:158) */
+    uint8_t *queues;      /* [S][queue_width] action queues (agents.py:32) */
+    int64_t *status;      /* [S] RC_ROLLOUT_* */
+    int64_t *steps;       /* [S] moves made = len(agent) = len(action_queue) (agents.py:34,37) */
+} rc_rollout_t;
+size_t rc_rollout_struct_bytes(void);
+
+/* For i < n, slot slots[i] (device int32 list) restarts from roots_soa column first_col + i (agents.py:26-29): steps 0, status
+ * RC_ROLLOUT_RUNNING or, for the solved cube, RC_ROLLOUT_ROOT_SOLVED; with_children also writes the slot's 12 children and their
+ * solved flags (what the first value step reads).  Other slots are not touched, nor is anything written for a listed index
+ * outside 0 .. n_slots - 1.  Needs stride >= first_col + n. */
+int rc_rollout_plant(const rc_rollout_t *r, const int32_t *slots, uint32_t n, const int8_t *roots_soa, size_t stride, size_t first_col,
+                     int with_children, rc_stream_t stream);
+/* One move of every running game by RandomSearch._step (agents.py:83-86) or PolicySearch._step (:138-142), in one launch.  The
+ * action of game g is decisions_row[g] if that is 0 .. 11 (decisions_row NULL: every byte is RC_ROLLOUT_POLICY).  Otherwise,
+ * with uniforms_row (double [S]), it is np.random.choice(12, p=softmax(logits)) for the double u = uniforms_row[g] that call
+ * would draw: the fp32 softmax with the row maximum subtracted, its running sum in double divided by the total, and the number
+ * of entries <= u, at most 11 (cdf.searchsorted(u, side="right")); a NaN probability ends the game RC_ROLLOUT_BAD_POLICY.
+ * Without uniforms_row it is the first maximum of the 12 logits as np.argmax finds it (a NaN is the maximum) -- the reference
+ * takes the maximum of their fp32 softmax, which differs only where the softmax rounds two distinct logits to one probability.
+ * Then the cube is turned, the action appended to the queue row (a byte that does not fit: RC_ROLLOUT_QUEUE_FULL, nothing is
+ * written and the cube stays), steps incremented, and the game is RC_ROLLOUT_SOLVED if the new state is the solved cube, else
+ * RC_ROLLOUT_EXHAUSTED if steps == max_steps.  `head` is [S][ld], 12 logits first, float or bf16, ld >= 13 (what
+ * rc_mcts_step_head and rc_egvm_step read); it may be NULL where every decision byte is an action -- a byte that asks a
+ * network that is not there ends the game RC_ROLLOUT_BAD_POLICY. */
+int rc_rollout_step_policy(const rc_rollout_t *r, const void *head, size_t ld, int head_is_bf16, const uint8_t *decisions_row,
+                           const double *uniforms_row, uint64_t max_steps, rc_stream_t stream);
+/* One move of every running game by ValueSearch._step (agents.py:156-166): the first child whose kid_solved flag is set, which
+ * ends the game RC_ROLLOUT_SOLVED (:158-161), else the first maximum of the game's 12 values, a NaN being the maximum (:165);
+ * values is float [12 S] in child order.  The child becomes the current state; queue byte, steps and RC_ROLLOUT_EXHAUSTED as
+ * above; and the 12 children of the new state with their solved flags are written for the next forward pass. */
+int rc_rollout_step_value(const rc_rollout_t *r, const float *values, uint64_t max_steps, rc_stream_t stream);
+/* Host only (no GPU needed): the next `steps` draws of n games from their own MT19937 streams, as in rc_egvm_draw (mt_keys,
+ * mt_pos, n_games, games, slots; generators are advanced as NumPy leaves them).  Game games[i] gets column slots[i] of a
+ * [steps][table_stride] table.  mode 0: bytes, as RandomState.randint(12) draws them (32-bit outputs masked to 4 bits until
+ * one is <= 11; agents.py:84).  mode 1: doubles, as RandomState.random_sample draws them (((a >> 5) 2^26 + (b >> 6)) / 2^53):
+ * the one number np.random.choice consumes (agents.py:140).  Every slots[i] must be < table_stride. */
+int rc_rollout_draw(uint32_t *mt_keys, int32_t *mt_pos, uint32_t n_games, const int32_t *games, const int32_t *slots, uint32_t n,
+                    int mode, uint32_t steps, void *table, size_t table_stride);
+
+/* Host only: game games[i] (i < n) gets the generator np.random.RandomState(seeds[games[i]]) starts with -- MT19937's
+ * init_genrand of the seed, pos 624 -- which is what np.random.seed(seed) right before the reference's `search` leaves.  seeds is
+ * int64 [n_games]; a listed seed outside 0 .. 2^32 - 1 (NumPy raises there) is RC_ERR_RANGE and nothing is written. */
+int rc_rollout_seed(uint32_t *mt_keys, int32_t *mt_pos, uint32_t n_games, const int32_t *games, uint32_t n, const int64_t *seeds);
+
 /* ---- breadth-first search (one problem per call sequence, GPU-wide levels) -----------------------
  *
  * Replaces the FIFO loop of librubiks/solving/agents.py:92-131 (class BFS) with level-synchronous

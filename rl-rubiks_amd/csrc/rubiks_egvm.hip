@@ -10,16 +10,9 @@
 #include <limits.h>
 
 #include "rubiks_common.h"
+#include "rubiks_rollout.h"
 
 namespace rubiks {
-
-__device__ __forceinline__ float egvm_head_elem(const void *head, size_t i, bool bf16) {
-    return bf16 ? __uint_as_float((u32) reinterpret_cast<const u16 *>(head)[i] << 16) : reinterpret_cast<const float *>(head)[i];
-}
-
-// "v replaces the best b" in a scan by ascending index that must end where np.argmax ends: on the first NaN if there is one,
-// else on the first maximum.
-__device__ __forceinline__ bool egvm_better(float v, float b) { return !isnan(b) && (isnan(v) || v > b); }
 
 // ---- one depth step (agents.py:690-716) ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_egvm_step(rc_egvm_t e, u32 d, const u8 *__restrict__ dec, const void *__restrict__ head,
@@ -216,28 +209,6 @@ __global__ __launch_bounds__(kBlock) void k_egvm_plant(rc_egvm_t e, const int *_
         e.hit[s] = RC_EGVM_NO_HIT;
     }
 }
-
-// ---- the host's draws: MT19937 as np.random.RandomState runs it (Matsumoto & Nishimura 1998) ------------------------------------
-struct Mt19937 {
-    u32 *key;
-    int pos;
-    u32 next() {
-        constexpr int N = 624, M = 397;
-        if (pos >= N) {
-            for (int k = 0; k < N; ++k) {
-                const u32 y = (key[k] & 0x80000000u) | (key[(k + 1) % N] & 0x7fffffffu);
-                key[k] = key[(k + M) % N] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-            }
-            pos = 0;
-        }
-        u32 y = key[pos++];
-        y ^= y >> 11;
-        y ^= (y << 7) & 0x9d2c5680u;
-        y ^= (y << 15) & 0xefc60000u;
-        y ^= y >> 18;
-        return y;
-    }
-};
 
 }  // namespace rubiks
 

@@ -25,6 +25,7 @@ from librubiks.solving import astar_device as ad
 from librubiks.solving import bfs_device as bd
 from librubiks.solving import egvm_device as ed
 from librubiks.solving import mcts_device as md
+from librubiks.solving import rollout_device as rd
 from librubiks.solving.results import BatchResult, QueueTable   # noqa: F401  (also this module's names: callers import them from here)
 from librubiks.utils import TickTock
 
@@ -942,14 +943,50 @@ class _StepAgent(Agent):
     `len(self) < max_states` test reads a counter that is updated after the loop, agents.py:30-38);
     here `max_states` additionally caps the number of moves per game, which keeps runs deterministic.
     All games of a batch step together; a finished game idles on the identity action.
+
+    `search` and a plain `search_batch` are driven move by move from the host and draw from the global np.random stream;
+    `search_batch(..., seeds=, slots=)` plays the games in lock step on the device, each on its own stream
+    (csrc/rubiks_rollout.hip, librubiks/solving/rollout_device.py).
     """
+    kind = None                # which game of rollout_device.KINDS the lock-step search plays
+    use_graph = True           # the lock-step search replays a round as one captured graph
+    steps_per_round = 8        # moves per round of the lock-step search: the host looks at the games once per round
+    QUEUE_STEPS = 64           # queue rows of a lock-step search bounded by time only start at this many moves and double between rounds
+    batch = None
+    batch_stats = None
 
     def _actions(self, cubes: DeviceCubes, running: torch.Tensor):
         """-> (uint8 actions [n_padded], bool solved_after [n]) for the current states."""
         raise NotImplementedError
 
+    def search_batch(self, states, time_limit: float = None, max_states: int = None, seeds=None, slots: int = None) -> BatchResult:
+        """
+        With neither `seeds` nor `slots`: the games step together, driven move by move from the host; random agents draw from the
+        global np.random stream, one draw per game and step in game order.  Otherwise the games run in lock step on the device
+        (librubiks/solving/rollout_device.py), `steps_per_round` moves between two looks of the host: game g draws from its own
+        stream np.random.RandomState(seeds[g]) and ends exactly -- solved flag, len(agent), action queue -- as the reference's
+        `search(states[g])` would right after np.random.seed(seeds[g]) if it stopped after `max_states` moves, whoever shares the
+        batch, however many slots there are and whatever `steps_per_round` is, wherever the network's rows do not depend on the
+        batch (the deterministic engine).  One difference remains for the greedy policy: the move is the first maximum of the 12
+        logits, where the reference takes the first maximum of their fp32 softmax (agents.py:139-140); the two differ only where
+        the softmax rounds two distinct logits to one probability.  The clock is looked at between rounds only, and
+        `time_limit` bounds the whole search.
+        seeds: integer array [G], or one integer s for RandomState(s).randint(0, 2**31 - 1, size=G); None (with `slots`): one
+        such call on the global stream at entry.  Agents that draw nothing accept it and ignore its values.
+        slots: play at most this many games at a time; finished games hand their slots to the scrambles still waiting
+        (continuous batching, as `AStar.search_batch`).  Games that never got a slot before the time limit end unsolved, with 0
+        nodes, status EXHAUSTED and 0 seconds.  `nodes`, `iterations` and the queue length of a game are its number of moves.
+        """
+        if seeds is None and slots is None:
+            return self._search_stepwise(states, time_limit, max_states)
+        roots = DeviceCubes.of(states)
+        if self.kind in rd.RolloutBatch.TABLE_DTYPE:
+            seeds = ed.game_seeds(seeds, roots.n)
+        time_limit, max_states = Agent.reset(self, time_limit, max_states)
+        return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
+
     @no_grad
-    def search_batch(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
+    def _search_stepwise(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
         time_limit, max_states = self.reset(time_limit, max_states)
         cubes = DeviceCubes.of(states)
         cubes = DeviceCubes(cubes.soa.clone(), cubes.n)
@@ -990,6 +1027,120 @@ class _StepAgent(Agent):
     def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
         return bool(self.search_batch(np.asarray(state)[None], time_limit, max_states).solved[0])
 
+    def _batch_for(self, n_slots: int, queue_width: int) -> "rd.RolloutBatch":
+        b, want = self.batch, (n_slots, self.kind, int(self.steps_per_round), bool(self.use_graph))
+        if b is None or (b.S, b.kind, b.K, b.use_graph) != want or b.Q < queue_width or b.Q > 4 * queue_width:
+            self.batch = None
+            torch.cuda.empty_cache()
+            b = self.batch = rd.RolloutBatch(*want[:3], queue_width, use_graph=want[3])
+        if self.kind != "random":
+            b.set_net(self._search_net(), self.net_dtype)   # every search: `net` may have been trained or replaced since the last one
+        return b
+
+    @no_grad
+    def _search_lockstep(self, roots: DeviceCubes, time_limit: float, max_states: int, seeds, slots) -> BatchResult:
+        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given)."""
+        by_states = not _unbounded(max_states)
+        cap = int(max_states) if by_states else DEFAULT_STEP_CAP
+        pool = SlotPool(roots.n, slots, self.tt.tock)
+        S, owner = pool.S, pool.owner
+        batch = self._batch_for(S, cap if by_states else min(cap, self.QUEUE_STEPS))
+        K = batch.K
+        streams = ed.GameStreams(seeds) if batch.table is not None else None   # every game's own np.random stream, started when it is planted
+        tables = batch.host_tables()
+        views = [None if t is None else t.numpy() for t in tables]
+        played = np.zeros(S, dtype=np.int64)              # moves queued for the slot's game so far
+        stats = self.batch_stats = {"rounds": 0, "draw_s": 0.0, "draw_exposed_s": 0.0, "wait_s": 0.0, "device_round_ms": []}
+
+        def draw(into, which):
+            """The next round's draws of the games in slots `which`."""
+            if streams is None:
+                return 0.0
+            t0 = perf_counter()
+            rd.draw(streams, owner[which], which, into)
+            dt = perf_counter() - t0
+            stats["draw_s"] += dt
+            return dt
+
+        def adopt(which):
+            if streams is not None:
+                rd.start(streams, owner[which])
+            played[which] = 0
+
+        def plant(into, first):
+            batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first)
+        self.tt.tick()
+        batch.reset(roots)                                # the first S scrambles; the others move in as games finish
+        words = batch.snapshot()
+        adopt(np.arange(S))
+        words[1].synchronize()
+        final = words[0].numpy().copy()
+        status = final[0]                                 # (root-solved games are known before the first round)
+        taken, r = [], 0
+        if (status == rd.RUNNING).any() or pool.waiting:
+            stats["draw_exposed_s"] += draw(views[0], np.flatnonzero(status == rd.RUNNING))
+            while True:
+                if not by_states:
+                    batch.grow_queues(min(cap, int(played.max()) + K))
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                batch.round(tables[r % 2], cap)
+                t1.record()
+                host, ev = batch.snapshot()
+                live = owner >= 0
+                played[live & (status == rd.RUNNING)] += K
+                # round r + 1 is drawn while round r runs, for every game that can still be running then: a game always makes K
+                # draws per round, so its move t uses draw t of its stream whatever ends the game sooner
+                draw(views[(r + 1) % 2], np.flatnonzero(live & (status == rd.RUNNING) & (played < cap)))
+                t_wait = perf_counter()
+                ev.synchronize()
+                stats["wait_s"] += perf_counter() - t_wait
+                stats["device_round_ms"].append(t0.elapsed_time(t1))
+                stats["rounds"] = r = r + 1
+                final = host.numpy().copy()
+                status = final[0]
+                if (status == rd.QUEUE_FULL).any():
+                    raise _hip.RubiksHipError(f"{self}: the queue row of slot {int(np.argmax(status == rd.QUEUE_FULL))} is full ({batch.Q} bytes)")
+                if (status == rd.BAD_POLICY).any():       # where np.random.choice raises (reference agents.py:140)
+                    raise ValueError(f"{self}: probabilities contain NaN (game {int(owner[np.argmax(status == rd.BAD_POLICY)])})")
+                now = self.tt.tock()
+                ended = live & (status != rd.RUNNING)
+                done = np.flatnonzero(ended)
+                pool.sighted(done, now)
+                if now >= time_limit or not (live & ~ended).any() and not pool.waiting:
+                    break
+                if pool.waiting and len(done):
+                    # the finished slots' results leave without waiting, then the waiting scrambles are planted there
+                    taken.append((owner[done].copy(), final[:, done].copy(), batch.take_queues(done, final[1, done].max())))
+                    fresh = pool.refill(done, plant)
+                    adopt(fresh)
+                    status[done] = rd.EXHAUSTED           # (an empty slot is not played)
+                    status[fresh] = rd.RUNNING            # (a solved scramble shows ROOT_SOLVED in the next block; its draws are not used)
+                    stats["draw_exposed_s"] += draw(views[r % 2], fresh)
+        torch.cuda.synchronize()
+        if batch.engine is not None and self._overflowed(batch.engine):   # the split engine could not represent an activation: the same search (same seeds) in fp32
+            return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
+        seconds = self.tt.tock()
+        left = np.flatnonzero(owner >= 0)
+        parts = [(games, self._part(w, q[0], q[1])) for games, w, q in taken]
+        if len(left):
+            w = final[:, left]
+            parts.append((owner[left], self._part(w, *batch.take_queues(left, w[1].max())[:2])))
+        result = BatchResult.merge(pool.n_games, parts, seconds)
+        result.status[result.status == rd.RUNNING] = rd.EXHAUSTED   # the time limit ended these
+        pool.close(result, seconds, rd.EXHAUSTED)
+        self._explored_states = int(result.nodes[0])
+        self.action_queue = result.queues[0]
+        return result
+
+    @staticmethod
+    def _part(words: np.ndarray, host: torch.Tensor, ev) -> BatchResult:
+        ev.synchronize()
+        status, steps = words
+        solved = (status == rd.SOLVED) | (status == rd.ROOT_SOLVED)
+        return BatchResult(solved, np.where(solved, steps, -1), steps.copy(), QueueTable(host.numpy().copy(), steps), 0.0, steps.copy(),
+                           status.copy())
+
 
 def _pad16(t: torch.Tensor) -> torch.Tensor:
     n = t.numel()
@@ -1000,6 +1151,7 @@ def _pad16(t: torch.Tensor) -> torch.Tensor:
 
 class RandomSearch(_StepAgent):
     """Uniformly random moves from np.random (reference agents.py:82-90); one draw per running game per step."""
+    kind = "random"
 
     def _actions(self, cubes, running):
         a = torch.from_numpy(np.random.randint(12, size=cubes.n).astype(np.uint8)).to(cubes.soa.device)
@@ -1010,8 +1162,13 @@ class RandomSearch(_StepAgent):
 
 
 class _DeepStepAgent(_StepAgent, DeepAgent):
-    def __init__(self, net, net_dtype=F32_SPLIT):
-        DeepAgent.__init__(self, net, net_dtype)
+    def __init__(self, net, net_dtype=F32_SPLIT, deterministic: bool = False, use_graph: bool = True, steps_per_round: int = 8):
+        """deterministic: as for `MCTS` -- one layer plan of the split engine for every row count, so a game of a lock-step search
+        (`search_batch` with `seeds` or `slots`) does not depend on which other games share its batch.
+        use_graph, steps_per_round: the lock-step search replays a round of that many (network pass, move) pairs as one
+        captured graph."""
+        DeepAgent.__init__(self, net, net_dtype, deterministic)
+        self.use_graph, self.steps_per_round = use_graph, steps_per_round
         self._engine = None
 
     def reset(self, time_limit, max_states):
@@ -1020,19 +1177,23 @@ class _DeepStepAgent(_StepAgent, DeepAgent):
         self._engine = make_inference_net(self._search_net(), self.net_dtype)   # rebuilt per search: weights may have been trained
         return out
 
-    def search_batch(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
-        res = _StepAgent.search_batch(self, states, time_limit, max_states)
+    def _search_stepwise(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
+        res = _StepAgent._search_stepwise(self, states, time_limit, max_states)
         if self._overflowed(self._engine):   # the split engine could not represent an activation: the same search in fp32
-            res = _StepAgent.search_batch(self, states, time_limit, max_states)
+            res = _StepAgent._search_stepwise(self, states, time_limit, max_states)
         return res
 
 
 class PolicySearch(_DeepStepAgent):
     """Follows the policy head: greedy argmax of softmax(policy), or samples it (reference agents.py:132-151)."""
 
-    def __init__(self, net, sample_policy=False, net_dtype=F32_SPLIT):
-        super().__init__(net, net_dtype)
+    def __init__(self, net, sample_policy=False, net_dtype=F32_SPLIT, **kw):
+        super().__init__(net, net_dtype, **kw)
         self.sample_policy = sample_policy
+
+    @property
+    def kind(self) -> str:
+        return "sampled" if self.sample_policy else "greedy"
 
     @classmethod
     def from_saved(cls, loc: str, use_best: bool, sample_policy=False, **kw):
@@ -1053,6 +1214,7 @@ class PolicySearch(_DeepStepAgent):
 
 class ValueSearch(_DeepStepAgent):
     """Moves to the child of highest value; a solved child is taken at once (reference agents.py:154-169)."""
+    kind = "value"
 
     def _actions(self, cubes, running):
         kids = cubes.expand12()

@@ -101,59 +101,11 @@ def queue_rounds(max_states: int, workers: int, depth: int) -> int:
     return int(max_states) // (workers * depth)
 
 
-class EGVMBatch:
-    def __init__(self, n_slots: int, workers: int, depth: int, queue_width: int, device=None, use_graph: bool = True):
-        self.lib = _hip.lib()
-        dev = device or torch.device("cuda", torch.cuda.current_device())
-        S, W, D = int(n_slots), int(workers), int(depth)
-        if not (S > 0 and 0 < W <= MAX_WORKERS and 0 < D <= MAX_DEPTH and S * W <= 1 << 30):
-            raise ValueError(f"EGVM batch: {S} slots, {W} workers (1 .. {MAX_WORKERS}), depth {D} (1 .. {MAX_DEPTH})")
-        self.S, self.W, self.D, self.device, self.use_graph = S, W, D, dev, bool(use_graph)
-        self.R = S * W
-        self.R16 = (self.R + 15) // 16 * 16
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
-        self.rows = DeviceCubes.empty(self.R, dev)                  # the workers' current states = network input
-        self.best = DeviceCubes.empty(self.R, dev)
-        self.best_value = z((self.R,), torch.float32)
-        self.best_depth = torch.full((self.R,), -1, dtype=torch.int32, device=dev)
-        self.paths = z((S, W, D), torch.uint8)
-        self.hit = torch.full((S,), -1, dtype=torch.int32, device=dev)      # RC_EGVM_NO_HIT
-        self.current = z((S, 20), torch.int8)
-        self.words = z((4, S), torch.int64)                         # status, nodes, queue_len, rounds: what the host reads per round
-        self.words[0] = EXHAUSTED                                   # nothing planted yet: no slot is played
-        self.status, self.nodes, self.queue_len, self.rounds = self.words
-        self.queues = z((S, max(1, int(queue_width))), torch.uint8)
-        self.decisions = torch.full((D, self.R16), POLICY, dtype=torch.uint8, device=dev)   # this round's table (static: graphs)
-        self.values_last = z((self.R,), torch.float32)
-        s = _EgStruct()
-        s.n_slots, s.workers, s.depth, s.stride = S, W, D, self.rows.stride
-        for name, src in (("rows_soa", self.rows.soa), ("best_soa", self.best.soa)):
-            setattr(s, name, src.data_ptr())
-        for name in ("best_value", "best_depth", "paths", "hit", "current", "status", "nodes", "queue_len", "rounds"):
-            setattr(s, name, getattr(self, name).data_ptr())
-        self.struct = s
-        self._set_queues(self.queues)
-        self.engine, self._net_fp = None, None
-        self._graphs, self._graph_pool = {}, None
+class LockstepBatch:
+    """What the device batches of the lock-step agents share (EGVMBatch, rollout_device.RolloutBatch): the engine for `net` and the
+    head (12 logits + value) of every row of `self.rows` (a DeviceCubes of `self.R` rows on `self.device`), the captured rounds, the
+    queue rows (`self.queues` [S, Q], named by `self.struct`) and the block of words the host reads per round (`self.words`)."""
 
-    @property
-    def Q(self) -> int:
-        return self.queues.shape[1]
-
-    def _set_queues(self, queues: torch.Tensor):
-        self.queues = queues
-        self.struct.queues, self.struct.queue_width = queues.data_ptr(), queues.shape[1]
-        self._graphs = {}   # (the captured rounds hold the old row address and width)
-
-    def grow_queues(self, width: int):
-        """Queue rows of at least `width` bytes (doubling): between two rounds, contents kept."""
-        if width <= self.Q:
-            return
-        wider = torch.zeros((self.S, max(int(width), 2 * self.Q)), dtype=torch.uint8, device=self.device)
-        wider[:, :self.Q] = self.queues
-        self._set_queues(wider)
-
-    # ---- network ---------------------------------------------------------------------------------
     def set_net(self, net, dtype=torch.bfloat16):
         """Builds the inference engine for `net`; a no-op when the batch already runs exactly these weights."""
         fp = net_fingerprint(net, dtype)
@@ -196,6 +148,94 @@ class EGVMBatch:
                 self._head_buf[lo:lo + n, :N_ACT + 1].copy_(out[:, :N_ACT + 1])
         return self._head_buf
 
+    @property
+    def Q(self) -> int:
+        return self.queues.shape[1]
+
+    def _set_queues(self, queues: torch.Tensor):
+        self.queues = queues
+        self.struct.queues, self.struct.queue_width = queues.data_ptr(), queues.shape[1]
+        self._graphs = {}   # (the captured rounds hold the old row address and width)
+
+    def grow_queues(self, width: int):
+        """Queue rows of at least `width` bytes (doubling): between two rounds, contents kept."""
+        if width <= self.Q:
+            return
+        wider = torch.zeros((self.S, max(int(width), 2 * self.Q)), dtype=torch.uint8, device=self.device)
+        wider[:, :self.Q] = self.queues
+        self._set_queues(wider)
+
+    def _run(self, limit: int):
+        """`self._round(limit)`: launched as it is, or -- `use_graph` -- as the replay of its captured graph; the first round of a
+        limit runs eagerly and is then captured (the capture records launches, it does not advance the search)."""
+        if not self.use_graph:
+            return self._round(limit)
+        g = self._graphs.get(limit)
+        if g is not None:
+            return g.replay()
+        self._round(limit)
+        torch.cuda.synchronize()
+        if self._graph_pool is None:
+            self._graph_pool = torch.cuda.graph_pool_handle()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._graph_pool):
+            self._round(limit)
+        self._graphs[limit] = g
+
+    def snapshot(self):
+        """(pinned int64 copy of `words` (per slot: status and the counters), event): the one block the host reads per round."""
+        host = torch.empty(self.words.shape, dtype=torch.int64, pin_memory=True)
+        host.copy_(self.words, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev
+
+    def take_queues(self, slots: np.ndarray, width: int):
+        """Queue rows of `slots`, their first `width` bytes, on their way into pinned memory: (host tensor, event, keep-alive)."""
+        idx = torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).pin_memory().to(self.device, non_blocking=True)
+        rows = self.queues[idx, :max(1, int(width))]
+        host = torch.empty(rows.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(rows, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return host, ev, (idx, rows)
+
+
+class EGVMBatch(LockstepBatch):
+    def __init__(self, n_slots: int, workers: int, depth: int, queue_width: int, device=None, use_graph: bool = True):
+        self.lib = _hip.lib()
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        S, W, D = int(n_slots), int(workers), int(depth)
+        if not (S > 0 and 0 < W <= MAX_WORKERS and 0 < D <= MAX_DEPTH and S * W <= 1 << 30):
+            raise ValueError(f"EGVM batch: {S} slots, {W} workers (1 .. {MAX_WORKERS}), depth {D} (1 .. {MAX_DEPTH})")
+        self.S, self.W, self.D, self.device, self.use_graph = S, W, D, dev, bool(use_graph)
+        self.R = S * W
+        self.R16 = (self.R + 15) // 16 * 16
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+        self.rows = DeviceCubes.empty(self.R, dev)                  # the workers' current states = network input
+        self.best = DeviceCubes.empty(self.R, dev)
+        self.best_value = z((self.R,), torch.float32)
+        self.best_depth = torch.full((self.R,), -1, dtype=torch.int32, device=dev)
+        self.paths = z((S, W, D), torch.uint8)
+        self.hit = torch.full((S,), -1, dtype=torch.int32, device=dev)      # RC_EGVM_NO_HIT
+        self.current = z((S, 20), torch.int8)
+        self.words = z((4, S), torch.int64)                         # status, nodes, queue_len, rounds: what the host reads per round
+        self.words[0] = EXHAUSTED                                   # nothing planted yet: no slot is played
+        self.status, self.nodes, self.queue_len, self.rounds = self.words
+        self.queues = z((S, max(1, int(queue_width))), torch.uint8)
+        self.decisions = torch.full((D, self.R16), POLICY, dtype=torch.uint8, device=dev)   # this round's table (static: graphs)
+        self.values_last = z((self.R,), torch.float32)
+        s = _EgStruct()
+        s.n_slots, s.workers, s.depth, s.stride = S, W, D, self.rows.stride
+        for name, src in (("rows_soa", self.rows.soa), ("best_soa", self.best.soa)):
+            setattr(s, name, src.data_ptr())
+        for name in ("best_value", "best_depth", "paths", "hit", "current", "status", "nodes", "queue_len", "rounds"):
+            setattr(s, name, getattr(self, name).data_ptr())
+        self.struct = s
+        self._set_queues(self.queues)
+        self.engine, self._net_fp = None, None
+        self._graphs, self._graph_pool = {}, None
+
     # ---- search phases ---------------------------------------------------------------------------
     def reset(self, roots: DeviceCubes):
         """Slot s starts from roots[s] (roots may hold more scrambles: the rest wait for `plant`)."""
@@ -225,35 +265,4 @@ class EGVMBatch:
         captured (the capture records launches, it does not advance the search); later rounds replay the graph."""
         assert decisions.dtype == torch.uint8 and tuple(decisions.shape) == (self.D, self.R16) and self.engine is not None
         self.decisions.copy_(decisions, non_blocking=True)
-        if not self.use_graph:
-            return self._round(max_states)
-        key = int(max_states)
-        g = self._graphs.get(key)
-        if g is not None:
-            return g.replay()
-        self._round(max_states)
-        torch.cuda.synchronize()
-        if self._graph_pool is None:
-            self._graph_pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._graph_pool):
-            self._round(max_states)
-        self._graphs[key] = g
-
-    def snapshot(self):
-        """(pinned int64 [4, S] copy of status / nodes / queue_len / rounds, event): the one block the host reads per round."""
-        host = torch.empty(self.words.shape, dtype=torch.int64, pin_memory=True)
-        host.copy_(self.words, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev
-
-    def take_queues(self, slots: np.ndarray, width: int):
-        """Queue rows of `slots`, their first `width` bytes, on their way into pinned memory: (host tensor, event, keep-alive)."""
-        idx = torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).pin_memory().to(self.device, non_blocking=True)
-        rows = self.queues[idx, :max(1, int(width))]
-        host = torch.empty(rows.shape, dtype=torch.uint8, pin_memory=True)
-        host.copy_(rows, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev, (idx, rows)
+        self._run(int(max_states))

@@ -36,9 +36,11 @@ def _world_size() -> int:
 class Evaluator:
     def __init__(self, n_games, scrambling_depths, max_time=None, max_states=None, logger=NullLogger(), slots: int = None):
         """
-        slots: for agents whose `search_batch` takes `slots` (MCTS, AStar): the games of ALL depths form one pool that
-        is searched with at most `slots` concurrent trees / A* problems, finished ones handing their place to waiting games
-        (continuous batching); `max_time`, if given, then bounds the whole pool at max_time x len(depths).
+        slots: for agents whose `search_batch` takes `slots` (MCTS, AStar, EGVM, RandomSearch, PolicySearch, ValueSearch): the
+        games of ALL depths form one pool that is searched with at most `slots` concurrent trees / A* problems / games, finished
+        ones handing their place to waiting games (continuous batching); `max_time`, if given, then bounds the whole pool at
+        max_time x len(depths).  Agents that draw random numbers then give every game a stream of its own, seeded by one
+        draw from the global stream after the scrambles (`search_batch(seeds=None)`).
         """
         self.n_games, self.max_time, self.max_states, self.slots = n_games, max_time, max_states, slots
         self.tt = TickTock()
