@@ -297,7 +297,8 @@ __global__ __launch_bounds__(kBlock) void k_astar_push_relax(rc_astar_t a, const
     const int first = a.n_nodes[b] - cnt + 1;
     if (tid == 0) s_won = 0;
     __syncthreads();
-    // win check on the new states only (agents.py:321); the lowest index is what indices[solved] finds
+    // win check on the new states only (agents.py:321).  New states are distinct, so at most one of them is the solved cube:
+    // the atomicMax elects nothing, it only carries that one index (> 0) to every lane
     u32 sw[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int j = 0; j < kPlanes; ++j) key_set(sw, j, (u32)(u8)kTables.solved[j]);

@@ -409,6 +409,12 @@ class Arena:
         assert self.layout[name][2] == np.uint8
         self.mem[self.layout[name][0] + index] = value
 
+    def write(self, name: str, index, value):
+        """array[index] = value on the flat array `name` in its own dtype (index: an int or a slice)."""
+        import torch
+        o, n, dt, _ = self.layout[name]
+        self.mem[o:o + n].view(getattr(torch, dt.name))[index] = value
+
 
 def egvm_arena(S, W, D, Q, stride, device="cuda"):
     """(Arena, filled egvm_device._EgStruct) for an S x W x D batch with queue rows of Q bytes."""
