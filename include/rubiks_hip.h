@@ -184,6 +184,13 @@ int rc_first_layer_split_flag_f16(const int8_t *soa, size_t n, size_t stride, co
  * runs (cube.py:265-277 + model.py:123-127,150-157); range_flag as above (may be NULL). */
 int rc_first_layer_gather_f16(const int8_t *soa, size_t n, size_t stride, const float *w_rows, const float *bias,
                               uint16_t *out_hi_lo, size_t H, int activation, float alpha, int32_t *range_flag, rc_stream_t stream);
+/* The same for packed rows: output row r is the layer of state src_map[r], for r < min(*rows_dev, n) only (both on the device,
+ * both or neither; src_map[r] < n).  The launch is shaped by n, the rows that exist are shared evenly among its workgroups; a
+ * state's outputs are the bits rc_first_layer_gather_f16 gives it.  form: 0 = by batch size, 1 / 2 = the small- / large-batch
+ * form of the kernel (same bits). */
+int rc_first_layer_gather_rows_f16(const int8_t *soa, size_t n, size_t stride, const float *w_rows, const float *bias,
+                                   uint16_t *out_hi_lo, size_t H, int activation, float alpha, int32_t *range_flag,
+                                   const uint32_t *rows_dev, const int32_t *src_map, int form, rc_stream_t stream);
 int rc_split_act_f16(const float *c, const float *c_corr, float corr_scale, size_t n_rows, size_t n_cols, const float *bias,
                      int activation, float alpha, uint16_t *out_hi_lo, float *out_f32, rc_stream_t stream);
 
@@ -201,6 +208,11 @@ int rc_split_gemm_partials_f16(const uint16_t *a_hi_lo, const uint16_t *w_lo_hi_
  * Replaces rc_split_act_f16's fp32 output + the 13-wide fp32 library GEMM (model.py:124-129,150-159 at fp32 accuracy). */
 int rc_head_split_f32(const float *c, const float *c_corr, float corr_scale, size_t n, size_t K, const float *bias_h,
                       int activation, float alpha, const float *w, const float *bias_o, size_t n_out, float *out, rc_stream_t stream);
+/* The same for packed rows: only rows r < min(*rows_dev, n) of c / c_corr exist, and row r's outputs go to row src_map[r] < n
+ * of out ([n][16]); rows of out that no r maps to are not written. */
+int rc_head_split_rows_f32(const float *c, const float *c_corr, float corr_scale, size_t n, size_t K, const float *bias_h,
+                           int activation, float alpha, const float *w, const float *bias_o, size_t n_out, float *out,
+                           const uint32_t *rows_dev, const int32_t *src_map, rc_stream_t stream);
 /* One hidden layer of that network as ONE kernel (own MFMA GEMM, fused epilogue; csrc/rubiks_gemm.hip):
  *   y = act(hi_x W_hi^T + 2^-11 (hi_x W_lo^T + lo_x W_hi^T) + bias)          (model.py:123-127,150-157 at fp32 accuracy)
  * a_hi_lo: [n_rows][2 k] halves (hi | lo), as the kernels above write it;  w_lo_hi_hi: [n_out][3 k] halves, the layer's
@@ -244,6 +256,9 @@ typedef struct rc_split_layer {
     int32_t *range_flag;        /* optional */
     int products;               /* rc_split_layer_f16: 0 / 3 = the three products of the split layer; 1 = ONE f16 product of a [n_rows][k]
                                  * and w [n_out][k] as they are (the input layer: a = [onehot | 2^-11 onehot], w = [W_hi | W_lo], k = 960) */
+    const uint32_t *rows_dev;   /* optional (rc_split_layer_f16; tile 1 / 3, or out_partials): a device word R.  Only rows < min(R, n_rows) exist: the
+                                 * grid stays the one n_rows gives, each of its row tiles takes an even share of the R rows in whole 16-row
+                                 * fragments, rows >= R are neither computed nor written.  Rows < R get the bits a plain launch gives them. */
 } rc_split_layer_t;
 size_t rc_split_layer_struct_bytes(void);
 int rc_split_layer_f16(const rc_split_layer_t *layer, rc_stream_t stream);
@@ -257,6 +272,11 @@ int rc_split_layer_corr_chunks(size_t k, int k_splits);   /* host only; -1 on a 
 int rc_split_reduce_f16(const float *partials, size_t partial_stride, int n_partials, int n_corr, size_t n_rows, size_t n_cols,
                         const float *bias, const uint16_t *residual_hi_lo, int activation, float alpha, const float *post_scale,
                         const float *post_shift, uint16_t *out_hi_lo, float *out_f32, int32_t *range_flag, rc_stream_t stream);
+/* The same on the rows < min(*rows_dev, n_rows) only (a device word); the others are neither read nor written. */
+int rc_split_reduce_rows_f16(const float *partials, size_t partial_stride, int n_partials, int n_corr, size_t n_rows, size_t n_cols,
+                             const float *bias, const uint16_t *residual_hi_lo, int activation, float alpha, const float *post_scale,
+                             const float *post_shift, uint16_t *out_hi_lo, float *out_f32, int32_t *range_flag,
+                             const uint32_t *rows_dev, rc_stream_t stream);
 
 /* ---- network head: last activation + skinny output layer in one pass -----------------------------------------
  * out[i][o] = bias[o] + sum_k w[o][k] * act(x[i][k])   for o < n_out <= 16   (float out, row pitch 16)
@@ -454,6 +474,13 @@ int rc_mcts_step(const rc_mcts_t *m, const float *probs, const float *values, do
                  rc_stream_t stream);
 int rc_mcts_step_head(const rc_mcts_t *m, const void *head, size_t ld, int head_is_bf16, double c, uint32_t level_budget,
                       uint32_t max_states, rc_stream_t stream);
+/* The network rows that hold a state, packed.  The tree at list position i fills the first cnt(i) of its 11 row slots: 0 if it
+ * did not expand, 11 / 2 in the two root phases, else the number of its new children.  One workgroup scans the counts in list
+ * order:  first[i] = sum of cnt(j < i),  *rows = R = their total,  src[first[i] + j] = 11 i + j  (first: [list length], src:
+ * [11 x list length], all on the device).  No atomics: the placement is a function of the list and the trees' state alone.  The
+ * network then runs on the R packed rows (rc_first_layer_gather_rows_f16, rc_split_layer_t::rows_dev, rc_split_reduce_rows_f16)
+ * and rc_head_split_rows_f32 writes every output to its row slot: the tree kernels read the layout they always read. */
+int rc_mcts_row_map(const rc_mcts_t *m, uint32_t *rows, int32_t *first, int32_t *src, rc_stream_t stream);
 /* _complete_graph (agents.py:597-611) for every tree with status RC_MCTS_SOLVED: each leaf is linked, both
  * ways, to those of its 12 children that already exist in the tree (looked up in the tree's hash table). */
 int rc_mcts_complete_graph(const rc_mcts_t *m, rc_stream_t stream);

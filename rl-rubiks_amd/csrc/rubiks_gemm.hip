@@ -62,6 +62,7 @@ struct GemmArgs {
     int *flag;                   // kOutHalves: OR-ed with 1 when an output leaves IEEE half's range (|y| > 65504 or not finite)
     u32 S;                       // kPartials: number of K chunks (workgroups per tile)
     u32 P;                       // products of the f16 kinds: 3 = the split layer (a hi | lo, w lo | hi | hi), 1 = a [M][K] x w [N][K] as they are
+    const u32 *rows_dev;         // DYN kernels: device count R <= M of rows that exist (the packed rows of an MCTS step), see k_split_gemm
 };
 constexpr float kHalfMax = 65504.0f;
 
@@ -96,7 +97,13 @@ template <int WM, int WN, int MR, int NR> struct GemmTile {
 // 1 the rest of them (scaled by 2^-11 inside, as always) plus the main product, so y = act(out[1] + 2^-11 out[0] + bias) --
 // exactly what rc_head_split_f32 / rc_split_act_f16 compute from (c, c_corr).  For layers too narrow to fill the chip with
 // 352 x 256 tiles (the 2048 -> 1024 layer: 128 tiles).
-template <int WM, int WN, int MR, int NR, int ACT, int KIND>
+//
+// DYN: only the first R = *g.rows_dev of the M rows exist (R is known on the device alone: the packed child rows of an MCTS step).
+// The grid is the one the host chose from M; the kernel spreads the R rows evenly over its ceil(M / BM) row tiles, in whole
+// 16-row fragments -- tile tm holds rows tm h .. tm h + h - 1, h = 16 ceil(R / (16 row tiles)) <= BM -- and a wave leaves out the
+// fragment rows beyond h (their reads, MFMAs and epilogue; the LDS-DMA pieces of activation rows no fragment reads are not issued).
+// Rows >= R are neither computed nor written.  The K order of an output is the same: the bits of rows < R do not depend on R.
+template <int WM, int WN, int MR, int NR, int ACT, int KIND, bool DYN = false>
 __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
     using T = GemmTile<WM, WN, MR, NR>;
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
@@ -112,11 +119,21 @@ __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
     const u32 n_tiles = KIND == kPartials ? nwg / g.S : nwg;
     const u32 half = wg_all / n_tiles, wg = wg_all % n_tiles;   // kPartials: K chunk `half` of S; the first n_tiles workgroups of the (XCD-ordered) grid walk chunk 0
     const u32 tm = wg / nn, tn = wg % nn;
-    const size_t row0 = (size_t)tm * T::BM;
+    u32 M = g.M, tile_h = T::BM;   // rows of the launch, rows per tile
+    if (DYN) {
+        const u32 row_tiles = (g.M + T::BM - 1) / T::BM;
+        M = min((u32)__builtin_amdgcn_readfirstlane((int)*g.rows_dev), g.M);
+        tile_h = min(16u * ((M + 16u * row_tiles - 1) / (16u * row_tiles)), (u32)T::BM);
+        if (tm * tile_h >= M) return;   // (the whole workgroup: no barrier has been met)
+    }
+    const size_t row0 = (size_t)tm * tile_h;
+    const u32 tile_rows = min(tile_h, (u32)(M - row0));                                 // DYN: rows of this tile that exist, ...
+    const u32 frag_rows = (tile_rows + 15) / 16;                                        // ... its 16-row fragments ...
+    const u32 mr_n = frag_rows > wr * MR ? min(frag_rows - wr * MR, (u32)MR) : 0u;      // ... and those of this wave (wave-uniform)
     const u32 col0 = tn * T::BN;
     const bool one = KIND == kBf16 || g.P == 1;   // one product: a is [M][K], w is [N][K]
     const u32 K = g.K, lda = (one ? 1 : 2) * K * 2, ldw = (one ? 1 : 3) * K * 2;   // bytes
-    const u32 last_row = (u32)(g.M - 1 - row0);            // rows past M re-read the last row; their outputs are not stored
+    const u32 last_row = DYN ? tile_rows - 1 : (u32)(g.M - 1 - row0);   // rows past the end re-read the last row; their outputs are not stored
 
     // A wave's LDS-DMA pieces (8 rows x 128 bytes each): its activation pieces first (PA of them: piece p = i WAVES + wave of the
     // tile's BM / 8), then its weight pieces.  Each is ONE buffer_load ... lds: the tile's rows as a buffer resource (scalar
@@ -141,7 +158,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
             const u32 p = (i < PA ? i : i - PA) * DW + wave;
             if (wave >= (u32)DW) continue;
             if (i < PA) {
-                if (p < (u32)(T::BM / 8)) lds_dma16(sb.a, (lds_void *)(dst + p * 1024), src_off[i], a_col * 2);
+                if (p < (DYN ? 2 * frag_rows : (u32)(T::BM / 8))) lds_dma16(sb.a, (lds_void *)(dst + p * 1024), src_off[i], a_col * 2);
             } else if (p < (u32)(T::BN / 8)) {
                 lds_dma16(sb.w, (lds_void *)(dst + T::A_BYTES + p * 1024), src_off[i], kk * 2);
             }
@@ -191,6 +208,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
         for (int kh = 0; kh < 2; ++kh) xf[0][kh] = *reinterpret_cast<const f16x8 *>(s + x_off[kh]);
 #pragma unroll
         for (int m = 0; m < MR; ++m) {
+            if (!DYN || (u32)m < mr_n) {   // (DYN: a fragment row beyond the tile's rows is left out by the whole wave; the pieces below are not)
             if (m + 1 < MR) {
 #pragma unroll
                 for (int kh = 0; kh < 2; ++kh) xf[(m + 1) & 1][kh] = *reinterpret_cast<const f16x8 *>(s + x_off[kh] + (m + 1) * 16 * kGemmRowBytes);
@@ -201,6 +219,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
                 for (int n = 0; n < NR; ++n)
                     acc[m][n] = KIND == kBf16 ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[n][kh]), __builtin_bit_cast(bf16x8, xf[m & 1][kh]), acc[m][n], 0, 0, 0)
                                               : __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[n][kh], xf[m & 1][kh], acc[m][n], 0, 0, 0);
+            }
             // the next stage, two LDS-DMA pieces behind each of the first rows' MFMAs: issued in the shadow of the matrix cores
             // (and of the SIMD's other wave) instead of all at once behind the barrier, early enough to land before the next one
             if (more && kPiecesPerRow * m < PA + PW) stage(ks + 1, (ks + 1 - ks0) & 1, kPiecesPerRow * m, kPiecesPerRow * (m + 1));
@@ -225,7 +244,8 @@ __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
         const size_t row = row0 + wr * MR * 16 + m * 16 + fr;
-        if (row >= g.M) continue;
+        if (DYN && (u32)m >= mr_n) break;
+        if (DYN ? wr * MR * 16 + m * 16 + fr >= tile_rows : row >= g.M) continue;
         if ((RUBIKS_GEMM_ABLATE & 8) && acc[m][0][0] != 1.2345e-30f) continue;    // (8: no epilogue at all -- what the epilogue costs)
 
 #pragma unroll
@@ -286,24 +306,24 @@ __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
     if (KIND == kOutHalves && g.flag && out_of_range) atomicOr(g.flag, 1);
 }
 
-template <int WM, int WN, int MR, int NR, int ACT, int KIND> static int launch_split_gemm(const GemmArgs &g, hipStream_t s) {
+template <int WM, int WN, int MR, int NR, int ACT, int KIND, bool DYN = false> static int launch_split_gemm(const GemmArgs &g, hipStream_t s) {
     using T = GemmTile<WM, WN, MR, NR>;
     static std::atomic<unsigned long long> attr_set{0};   // per device: the attribute belongs to the function ON A DEVICE
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (!((attr_set.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_split_gemm<WM, WN, MR, NR, ACT, KIND>,
+        hipError_t e = hipFuncSetAttribute((const void *)k_split_gemm<WM, WN, MR, NR, ACT, KIND, DYN>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
         if (e != hipSuccess) return hip_rc(e);
         attr_set.fetch_or(1ull << (dev & 63), std::memory_order_release);
     }
     const u32 grid = (u32)(ceil_div((size_t)g.M, (size_t)T::BM) * (g.N / T::BN)) * (KIND == kPartials ? g.S : 1u);
-    hipLaunchKernelGGL((k_split_gemm<WM, WN, MR, NR, ACT, KIND>), dim3(grid), dim3(T::THREADS), T::LDS_BYTES, s, g);
+    hipLaunchKernelGGL((k_split_gemm<WM, WN, MR, NR, ACT, KIND, DYN>), dim3(grid), dim3(T::THREADS), T::LDS_BYTES, s, g);
     return launch_status();
 }
 
-template <int WM, int WN, int MR, int NR, int KIND> static int dispatch_split_gemm(const GemmArgs &g, int act, hipStream_t s) {
-#define RC_GEMM_ACT(ACT) launch_split_gemm<WM, WN, MR, NR, ACT, KIND>(g, s)
+template <int WM, int WN, int MR, int NR, int KIND, bool DYN = false> static int dispatch_split_gemm(const GemmArgs &g, int act, hipStream_t s) {
+#define RC_GEMM_ACT(ACT) launch_split_gemm<WM, WN, MR, NR, ACT, KIND, DYN>(g, s)
     if (act == RC_ACT_ELU) return RC_GEMM_ACT(RC_ACT_ELU);
     if (act == RC_ACT_RELU) return RC_GEMM_ACT(RC_ACT_RELU);
     return RC_GEMM_ACT(RC_ACT_NONE);
@@ -338,6 +358,7 @@ static int layer_args(const rc_split_layer_t *L, GemmArgs &g) {
     g.S = 1;
     RC_REQUIRE(L->products == 0 || L->products == 1 || L->products == 3, RC_ERR_RANGE);
     g.P = L->products == 1 ? 1u : 3u;
+    g.rows_dev = L->rows_dev;
     return RC_OK;
 }
 
@@ -357,6 +378,11 @@ extern "C" int rc_split_layer_f16(const rc_split_layer_t *L, rc_stream_t stream)
         g.out = (void *)L->out_partials;
         g.S = S;
         g.bias = nullptr;
+        if (g.rows_dev) {   // the same grids; rows beyond the device's count are left out
+            if (L->tile == 3) return launch_split_gemm<2, 4, 11, 2, RC_ACT_NONE, kPartials, true>(g, s);
+            if (L->tile == 7) return launch_split_gemm<2, 4, 11, 1, RC_ACT_NONE, kPartials, true>(g, s);
+            return launch_split_gemm<2, 4, 11, 4, RC_ACT_NONE, kPartials, true>(g, s);
+        }
         if (L->tile == 3) return launch_split_gemm<2, 4, 11, 2, RC_ACT_NONE, kPartials>(g, s);   // 352 x 128 tiles: small batches
         if (L->tile == 7) return launch_split_gemm<2, 4, 11, 1, RC_ACT_NONE, kPartials>(g, s);   // 352 x 64: fewer, deeper chunks for one row tile
         return launch_split_gemm<2, 4, 11, 4, RC_ACT_NONE, kPartials>(g, s);
@@ -370,6 +396,11 @@ extern "C" int rc_split_layer_f16(const rc_split_layer_t *L, rc_stream_t stream)
     if (tile == 0) tile = (L->n_out % 256 == 0 && row_tiles * (L->n_out / 256) >= 192) ? 1 : (row_tiles * (L->n_out / 128) >= 192) ? 3 : 2;
     RC_REQUIRE((tile != 1 && tile < 4) || L->n_out % 256 == 0, RC_ERR_RANGE);
     const int activation = L->activation;
+    if (g.rows_dev) {   // a device row count: the 8-wave 352-row tiles (what SplitF32Net plans for whole-K layers)
+        RC_REQUIRE(tile == 1 || tile == 3, RC_ERR_RANGE);
+        if (tile == 1) return split ? dispatch_split_gemm<2, 4, 11, 4, kOutHalves, true>(g, activation, s) : dispatch_split_gemm<2, 4, 11, 4, kOutF32, true>(g, activation, s);
+        return split ? dispatch_split_gemm<2, 4, 11, 2, kOutHalves, true>(g, activation, s) : dispatch_split_gemm<2, 4, 11, 2, kOutF32, true>(g, activation, s);
+    }
     if (tile == 6)   // 256 x 256 by four waves, 128 x 128 per wave: the accumulators are exactly the 256 AGPRs
         return split ? dispatch_split_gemm<2, 2, 8, 8, kOutHalves>(g, activation, s) : dispatch_split_gemm<2, 2, 8, 8, kOutF32>(g, activation, s);
     // 352 x 256 by FOUR waves, one per SIMD, accumulators in the upper half of the 512-register file: 176 x 128 per wave (tile 4:
@@ -409,6 +440,7 @@ extern "C" int rc_gemm_layer_bf16(const rc_split_layer_t *L, rc_stream_t stream)
     if (int rc = layer_args(L, g)) return rc;
     if (L->n_rows == 0) return RC_OK;
     RC_REQUIRE(L->bias && L->out_bf16 && !L->out_hi_lo && !L->out_f32 && !L->out_partials, RC_ERR_NULL);
+    RC_REQUIRE(L->rows_dev == nullptr, RC_ERR_RANGE);
     RC_REQUIRE(L->tile == 0 || L->tile == 1 || L->tile == 3 || L->tile == 4, RC_ERR_RANGE);
     g.out = (void *)L->out_bf16;
     int tile = L->tile;

@@ -1539,6 +1539,54 @@ __global__ __launch_bounds__(kBlock) void k_mcts_rehash(rc_mcts_t m, const rc_mc
     }
 }
 
+// ---- row map: the network rows of a step that hold a state, packed -------------------------------------------------------
+// The tree at list position i fills the first cnt(i) of its 11 row slots: none if it did not expand, the root and children 0..9
+// in phase ROOT_A, children 10 and 11 in ROOT_B, else its new children (backup_children reads exactly these).  One workgroup
+// scans the counts in LIST ORDER -- first[i] = sum of cnt(j < i), *rows = their total R -- and names the slot behind every packed
+// row: src[first[i] + j] = 11 i + j.  The placement is a function of the list and the trees' words alone (no atomics, no finish
+// order); the network then runs on R rows instead of 11 G and the head scatters its outputs back to the slots.
+constexpr int kMapBlock = 1024;
+__global__ __launch_bounds__(kMapBlock) void k_mcts_row_map(rc_mcts_t m, u32 n_list, u32 *__restrict__ rows, int *__restrict__ first,
+                                                            int *__restrict__ src) {
+    __shared__ u32 s_wave[kMapBlock / kWave];
+    __shared__ u32 s_base;
+    const u32 tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (u32 i0 = 0; i0 < n_list; i0 += kMapBlock) {
+        const u32 i = i0 + tid;
+        u32 cnt = 0;
+        if (i < n_list) {
+            const int t = tree_of(m, i);
+            if (t >= 0) {   // (the three words are requested together: one memory round trip behind the list's, not three)
+                const u32 expanded = m.expanded[t], newm = m.new_mask[t];
+                const int ph = m.phase[t] & kPhaseMask;
+                const u32 rows_of_phase = ph == kPhaseRootA ? 11u : ph == kPhaseRootB ? 2u : min((u32)__popc(newm & 0xFFFu), 11u);
+                cnt = expanded ? rows_of_phase : 0u;
+            }
+        }
+        u32 incl = cnt;   // inclusive scan inside the wave, the waves' totals through LDS
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const u32 up = __shfl_up(incl, d, kWave);
+            if (lane >= (u32)d) incl += up;
+        }
+        if (lane == kWave - 1) s_wave[wv] = incl;
+        __syncthreads();
+        u32 before = s_base;
+        for (u32 w = 0; w < wv; ++w) before += s_wave[w];
+        const u32 at = before + incl - cnt;
+        if (i < n_list) {
+            first[i] = (int)at;
+            for (u32 j = 0; j < cnt; ++j) src[at + j] = (int)(i * 11u + j);
+        }
+        __syncthreads();   // everyone has read s_base and s_wave
+        if (tid == kMapBlock - 1) s_base = before + incl;
+        __syncthreads();
+    }
+    if (tid == 0) *rows = s_base;
+}
+
 }  // namespace rubiks
 
 using namespace rubiks;
@@ -1753,6 +1801,13 @@ int rc_mcts_step_head(const rc_mcts_t *m, const void *head, size_t ld, int head_
     else if (nt == 512) RC_STEP(512);
     else RC_STEP(256);
 #undef RC_STEP
+    return launch_status();
+}
+
+int rc_mcts_row_map(const rc_mcts_t *m, uint32_t *rows, int32_t *first, int32_t *src, rc_stream_t stream) {
+    if (int rc = check_mcts(m)) return rc;
+    RC_REQUIRE(rows && first && src, RC_ERR_NULL);
+    hipLaunchKernelGGL(k_mcts_row_map, dim3(1), dim3(kMapBlock), 0, (hipStream_t)stream, *m, mcts_grid(m), rows, (int *)first, (int *)src);
     return launch_status();
 }
 

@@ -443,9 +443,10 @@ __global__ __launch_bounds__(kBlock) void k_split_reduce(const float4 *__restric
                                                          size_t n_rows, size_t n_cols, const float4 *__restrict__ bias,
                                                          const uint4 *__restrict__ res, float alpha, const float4 *__restrict__ post_scale,
                                                          const float4 *__restrict__ post_shift, uint4 *__restrict__ out_hl,
-                                                         float4 *__restrict__ out_f32, int *__restrict__ flag) {
+                                                         float4 *__restrict__ out_f32, int *__restrict__ flag, const u32 *__restrict__ rows_dev) {
     const size_t chunks = n_cols / 8;
     bool out_of_range = false;
+    if (rows_dev) n_rows = min((size_t)*rows_dev, n_rows);   // only the first *rows_dev rows exist (the packed rows of an MCTS step)
     for (size_t idx = (size_t)blockIdx.x * kBlock + threadIdx.x; idx < n_rows * chunks; idx += (size_t)gridDim.x * kBlock) {
         const size_t r = idx / chunks, ch = idx - r * chunks;
         float y[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -524,10 +525,13 @@ __global__ __launch_bounds__(kBlock) void k_split_reduce(const float4 *__restric
 // k = 16 j + 4 g .. + 3, and MFMA step s of block j contracts the s-th element of every chunk -- a permutation of k that
 // A (activations) and B (weights) share.  It replaces rc_split_act_f16's fp32 output + the library's 13-wide fp32 GEMM:
 // the [n][K] activation matrix (46 MB at n = 11 264) is neither written nor read back.
-template <int ACT, int KB>
+// MAP: only the first *rows_dev <= n rows exist, and row r's outputs go to row src_map[r] of `out` (the packed rows of an MCTS step
+// back at their trees' row slots); rows of `out` that no existing row maps to are not written.
+template <int ACT, int KB, bool MAP = false>
 __global__ __launch_bounds__(kBlock) void k_head_split(const float4 *__restrict__ c, const float4 *__restrict__ c_corr, float corr_scale,
                                                        size_t n, const float4 *__restrict__ bias_h, float alpha, const float4 *__restrict__ w,
-                                                       const float *__restrict__ bias_o, u32 n_out, float *__restrict__ out) {
+                                                       const float *__restrict__ bias_o, u32 n_out, float *__restrict__ out,
+                                                       const u32 *__restrict__ rows_dev, const int *__restrict__ src_map) {
     __shared__ float s_part[kBlock / kWave][16][17];
     constexpr int K = 64 * KB, K4 = K / 4;          // floats, float4 chunks per row; a wave owns K / 4 consecutive floats = KB blocks of 16
     const u32 tid = threadIdx.x, wv = tid / kWave, lane = tid & (kWave - 1), r = lane & 15, g = lane >> 4;
@@ -538,6 +542,8 @@ __global__ __launch_bounds__(kBlock) void k_head_split(const float4 *__restrict_
         wf[j] = r < n_out ? w[(size_t)r * K4 + chunk0 + 4 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
         bh[j] = bias_h[chunk0 + 4 * j];
     }
+    const size_t n_slots = n;   // rows of `out`
+    if (MAP) n = min((size_t)*rows_dev, n);
     const size_t n_tiles = ceil_div(n, (size_t)16);
     for (size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const size_t row = tile * 16 + r;
@@ -573,7 +579,10 @@ __global__ __launch_bounds__(kBlock) void k_head_split(const float4 *__restrict_
             const u32 orow = tid >> 4, o = tid & 15;
             const float v = (s_part[0][orow][o] + s_part[1][orow][o]) + (s_part[2][orow][o] + s_part[3][orow][o]);
             const size_t grow = tile * 16 + orow;
-            if (grow < n) out[grow * kHeadMaxOut + o] = (o < n_out) ? v + bias_o[o] : 0.f;
+            if (grow < n) {
+                const size_t dst = MAP ? (size_t)(u32)src_map[grow] : grow;
+                if (!MAP || dst < n_slots) out[dst * kHeadMaxOut + o] = (o < n_out) ? v + bias_o[o] : 0.f;
+            }
         }
     }
 }
@@ -774,11 +783,14 @@ constexpr int kGaCols = 64, kGaRows = 480;
 #endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <int ACT, int WAVES, int C>
+// MAP: output row r is the layer of state src_map[r], for r < *rows_dev <= n only (the packed rows of an MCTS step).  The grid is
+// the one the host chose from n; the kernel shares the rows that exist among its row groups by the host's own rule.
+template <int ACT, int WAVES, int C, bool MAP = false>
 __global__ __launch_bounds__(WAVES * kWave) void k_first_layer_gather(const u8 *__restrict__ soa, size_t n, size_t stride,
                                                                      const float4 *__restrict__ w_rows, const float *__restrict__ bias,
                                                                      unsigned char *__restrict__ out, u32 H, u32 rows_per_block, float alpha,
-                                                                     int *__restrict__ range_flag) {
+                                                                     int *__restrict__ range_flag, const u32 *__restrict__ rows_dev,
+                                                                     const int *__restrict__ src_map) {
     static_assert(C == 4 || C == 8, "4 or 8 columns per lane");
     constexpr int R = C / 4;                  // 16-byte reads per table row and lane
     constexpr u32 kLanes = kGaCols / C;       // lanes per state
@@ -787,6 +799,12 @@ __global__ __launch_bounds__(WAVES * kWave) void k_first_layer_gather(const u8 *
     const u32 tid = threadIdx.x, lane = tid & 63;
     const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const u32 col_tiles = H / kGaCols, ct = blockIdx.x % col_tiles, rg = blockIdx.x / col_tiles;
+    const u32 last_state = (u32)(n - 1);
+    if (MAP) {
+        n = min((size_t)*rows_dev, n);
+        const u32 per_group = (u32)ceil_div(n, (size_t)(gridDim.x / col_tiles)), unit = per_group < WAVES * kStates ? kStates : WAVES * kStates;
+        rows_per_block = (per_group + unit - 1) / unit * unit;
+    }
     const size_t row_lo = (size_t)rg * rows_per_block;
     if (row_lo >= n) return;
     const size_t row_hi = (row_lo + rows_per_block < n) ? row_lo + rows_per_block : n;
@@ -817,7 +835,8 @@ __global__ __launch_bounds__(WAVES * kWave) void k_first_layer_gather(const u8 *
     const __amdgpu_buffer_rsrc_t planes = __builtin_amdgcn_make_buffer_rsrc((void *)soa, 0, (int)(u32)(kPlanes * stride), 0x00020000);
     const u32 last = (u32)(n - 1), pitch = (u32)stride;
     auto codes_of = [&](size_t t, u32 (&c)[kPlanes]) {
-        const u32 tv = t < n ? (u32)t : last;
+        u32 tv = t < n ? (u32)t : last;
+        if (MAP) tv = min((u32)src_map[tv], last_state);
 #pragma unroll
         for (int j = 0; j < kPlanes; ++j) c[j] = (RUBIKS_GATHER_ABLATE & 4) ? (tv + j) % 24u : (u32)__builtin_amdgcn_raw_buffer_load_b8(planes, tv, (u32)j * pitch, 0);
     };
@@ -929,9 +948,10 @@ extern "C" int rc_split_act_f16(const float *c, const float *c_corr, float corr_
     return launch_status();
 }
 
-extern "C" int rc_split_reduce_f16(const float *partials, size_t partial_stride, int n_partials, int n_corr, size_t n_rows, size_t n_cols,
-                                   const float *bias, const uint16_t *residual_hi_lo, int activation, float alpha, const float *post_scale,
-                                   const float *post_shift, uint16_t *out_hi_lo, float *out_f32, int32_t *range_flag, rc_stream_t stream) {
+static int split_reduce(const float *partials, size_t partial_stride, int n_partials, int n_corr, size_t n_rows, size_t n_cols,
+                        const float *bias, const uint16_t *residual_hi_lo, int activation, float alpha, const float *post_scale,
+                        const float *post_shift, uint16_t *out_hi_lo, float *out_f32, int32_t *range_flag, const uint32_t *rows_dev,
+                        rc_stream_t stream) {
     if (n_rows == 0 || n_cols == 0) return RC_OK;
     RC_REQUIRE(partials && bias && (out_hi_lo || out_f32), RC_ERR_NULL);
     RC_REQUIRE((post_scale == nullptr) == (post_shift == nullptr), RC_ERR_NULL);
@@ -944,7 +964,7 @@ extern "C" int rc_split_reduce_f16(const float *partials, size_t partial_stride,
 #define RC_LAUNCH_RED(ACT)                                                                                                       \
     hipLaunchKernelGGL(k_split_reduce<ACT>, grid, block, 0, s, (const float4 *)partials, partial_stride / 4, n_partials, n_corr, n_rows, \
                        n_cols, (const float4 *)bias, (const uint4 *)residual_hi_lo, alpha, (const float4 *)post_scale,                \
-                       (const float4 *)post_shift, (uint4 *)out_hi_lo, (float4 *)out_f32, (int *)range_flag)
+                       (const float4 *)post_shift, (uint4 *)out_hi_lo, (float4 *)out_f32, (int *)range_flag, rows_dev)
     if (activation == RC_ACT_ELU) RC_LAUNCH_RED(RC_ACT_ELU);
     else if (activation == RC_ACT_RELU) RC_LAUNCH_RED(RC_ACT_RELU);
     else RC_LAUNCH_RED(RC_ACT_NONE);
@@ -952,23 +972,42 @@ extern "C" int rc_split_reduce_f16(const float *partials, size_t partial_stride,
     return launch_status();
 }
 
-extern "C" int rc_head_split_f32(const float *c, const float *c_corr, float corr_scale, size_t n, size_t K, const float *bias_h,
-                                 int activation, float alpha, const float *w, const float *bias_o, size_t n_out, float *out,
-                                 rc_stream_t stream) {
+extern "C" int rc_split_reduce_f16(const float *partials, size_t partial_stride, int n_partials, int n_corr, size_t n_rows, size_t n_cols,
+                                   const float *bias, const uint16_t *residual_hi_lo, int activation, float alpha, const float *post_scale,
+                                   const float *post_shift, uint16_t *out_hi_lo, float *out_f32, int32_t *range_flag, rc_stream_t stream) {
+    return split_reduce(partials, partial_stride, n_partials, n_corr, n_rows, n_cols, bias, residual_hi_lo, activation, alpha, post_scale,
+                        post_shift, out_hi_lo, out_f32, range_flag, nullptr, stream);
+}
+
+extern "C" int rc_split_reduce_rows_f16(const float *partials, size_t partial_stride, int n_partials, int n_corr, size_t n_rows, size_t n_cols,
+                                        const float *bias, const uint16_t *residual_hi_lo, int activation, float alpha,
+                                        const float *post_scale, const float *post_shift, uint16_t *out_hi_lo, float *out_f32,
+                                        int32_t *range_flag, const uint32_t *rows_dev, rc_stream_t stream) {
+    RC_REQUIRE(rows_dev != nullptr, RC_ERR_NULL);
+    return split_reduce(partials, partial_stride, n_partials, n_corr, n_rows, n_cols, bias, residual_hi_lo, activation, alpha, post_scale,
+                        post_shift, out_hi_lo, out_f32, range_flag, rows_dev, stream);
+}
+
+static int head_split(const float *c, const float *c_corr, float corr_scale, size_t n, size_t K, const float *bias_h, int activation,
+                      float alpha, const float *w, const float *bias_o, size_t n_out, float *out, const uint32_t *rows_dev,
+                      const int32_t *src_map, rc_stream_t stream) {
     if (n == 0) return RC_OK;
-    RC_REQUIRE(c && bias_h && w && bias_o && out, RC_ERR_NULL);
+    RC_REQUIRE(c && bias_h && w && bias_o && out && (rows_dev == nullptr) == (src_map == nullptr), RC_ERR_NULL);
     RC_REQUIRE(aligned16(c) && aligned16(c_corr) && aligned16(bias_h) && aligned16(w), RC_ERR_ALIGN);
     RC_REQUIRE((K == 512 || K == 1024) && n_out >= 1 && n_out <= (size_t)kHeadMaxOut && activation >= RC_ACT_NONE && activation <= RC_ACT_ELU,
                RC_ERR_RANGE);
     const unsigned grid = grid_for(ceil_div(n, (size_t)16) * kBlock, kBlock, 256 * 4);
     hipStream_t s = (hipStream_t)stream;
-#define RC_LAUNCH_HS(ACT, KB)                                                                                                  \
-    hipLaunchKernelGGL((k_head_split<ACT, KB>), dim3(grid), dim3(kBlock), 0, s, (const float4 *)c, (const float4 *)c_corr, corr_scale, n, \
-                       (const float4 *)bias_h, alpha, (const float4 *)w, bias_o, (u32)n_out, out)
-#define RC_LAUNCH_HS_K(ACT)                   \
-    do {                                      \
-        if (K == 1024) RC_LAUNCH_HS(ACT, 16); \
-        else RC_LAUNCH_HS(ACT, 8);            \
+#define RC_LAUNCH_HS(ACT, KB, MAP)                                                                                             \
+    hipLaunchKernelGGL((k_head_split<ACT, KB, MAP>), dim3(grid), dim3(kBlock), 0, s, (const float4 *)c, (const float4 *)c_corr, corr_scale, \
+                       n, (const float4 *)bias_h, alpha, (const float4 *)w, bias_o, (u32)n_out, out, rows_dev, src_map)
+#define RC_LAUNCH_HS_K(ACT)                                     \
+    do {                                                        \
+        if (rows_dev) {                                         \
+            if (K == 1024) RC_LAUNCH_HS(ACT, 16, true);         \
+            else RC_LAUNCH_HS(ACT, 8, true);                    \
+        } else if (K == 1024) RC_LAUNCH_HS(ACT, 16, false);     \
+        else RC_LAUNCH_HS(ACT, 8, false);                       \
     } while (0)
     if (activation == RC_ACT_ELU) RC_LAUNCH_HS_K(RC_ACT_ELU);
     else if (activation == RC_ACT_RELU) RC_LAUNCH_HS_K(RC_ACT_RELU);
@@ -976,6 +1015,19 @@ extern "C" int rc_head_split_f32(const float *c, const float *c_corr, float corr
 #undef RC_LAUNCH_HS_K
 #undef RC_LAUNCH_HS
     return launch_status();
+}
+
+extern "C" int rc_head_split_f32(const float *c, const float *c_corr, float corr_scale, size_t n, size_t K, const float *bias_h,
+                                 int activation, float alpha, const float *w, const float *bias_o, size_t n_out, float *out,
+                                 rc_stream_t stream) {
+    return head_split(c, c_corr, corr_scale, n, K, bias_h, activation, alpha, w, bias_o, n_out, out, nullptr, nullptr, stream);
+}
+
+extern "C" int rc_head_split_rows_f32(const float *c, const float *c_corr, float corr_scale, size_t n, size_t K, const float *bias_h,
+                                      int activation, float alpha, const float *w, const float *bias_o, size_t n_out, float *out,
+                                      const uint32_t *rows_dev, const int32_t *src_map, rc_stream_t stream) {
+    RC_REQUIRE(rows_dev && src_map, RC_ERR_NULL);
+    return head_split(c, c_corr, corr_scale, n, K, bias_h, activation, alpha, w, bias_o, n_out, out, rows_dev, src_map, stream);
 }
 
 extern "C" int rc_first_layer_split_f16(const int8_t *soa, size_t n, size_t stride, const uint16_t *w_hi, const uint16_t *w_lo,
@@ -1022,12 +1074,14 @@ extern "C" int rc_first_layer_split_flag_f16(const int8_t *soa, size_t n, size_t
     return launch_status();
 }
 
-extern "C" int rc_first_layer_gather_f16(const int8_t *soa, size_t n, size_t stride, const float *w_rows, const float *bias,
-                                         uint16_t *out_hi_lo, size_t H, int activation, float alpha, int32_t *range_flag,
-                                         rc_stream_t stream) {
+// form: 0 = by batch size, 1 = sixteen waves x four columns per lane, 2 = eight waves x eight columns (tests force each)
+static int first_layer_gather(const int8_t *soa, size_t n, size_t stride, const float *w_rows, const float *bias, uint16_t *out_hi_lo,
+                              size_t H, int activation, float alpha, int32_t *range_flag, const uint32_t *rows_dev, const int32_t *src_map,
+                              int form, rc_stream_t stream) {
     if (n == 0) return RC_OK;
     RC_CHECK_SOA(soa, n, stride);
-    RC_REQUIRE(w_rows && bias && out_hi_lo, RC_ERR_NULL);
+    RC_REQUIRE(w_rows && bias && out_hi_lo && (rows_dev == nullptr) == (src_map == nullptr), RC_ERR_NULL);
+    RC_REQUIRE(form >= 0 && form <= 2, RC_ERR_RANGE);
     RC_REQUIRE(aligned16(w_rows) && aligned16(bias) && aligned16(out_hi_lo), RC_ERR_ALIGN);
     RC_REQUIRE(H >= (size_t)kGaCols && H % kGaCols == 0 && H < (1u << 24) && activation >= RC_ACT_NONE && activation <= RC_ACT_ELU, RC_ERR_RANGE);
     RC_REQUIRE(stride * kPlanes < (1ull << 32), RC_ERR_RANGE);   // the planes as ONE buffer resource: 32-bit offsets (214 M states per launch)
@@ -1036,7 +1090,7 @@ extern "C" int rc_first_layer_gather_f16(const int8_t *soa, size_t n, size_t str
     hipStream_t s = (hipStream_t)stream;
     // small batches: sixteen waves, four columns per lane (units of 4 states); large ones: eight waves, eight columns per lane.
     // A state's outputs are the same bits either way (the same additions in the same order).
-    const bool wide = n * col_tiles > (size_t)5000 * 64;
+    const bool wide = form ? form == 2 : n * col_tiles > (size_t)5000 * 64;
     const u32 waves = wide ? 8 : 16, states = wide ? 8 : 4;
     u32 row_groups = (256 + col_tiles - 1) / col_tiles;   // ~one workgroup per CU (the LDS slice allows no more)
     const u32 rows_per_pass = waves * states;
@@ -1044,24 +1098,28 @@ extern "C" int rc_first_layer_gather_f16(const int8_t *soa, size_t n, size_t str
     const u32 rows_per_block = (u32)round_up(per_group, per_group < rows_per_pass ? (size_t)states : (size_t)rows_per_pass);
     row_groups = (u32)ceil_div(n, (size_t)rows_per_block);
     const dim3 grid(col_tiles * row_groups);
-#define RC_LAUNCH_GA(ACT, WAVES, C)                                                                                   \
+#define RC_LAUNCH_GA(ACT, WAVES, C, MAP)                                                                                 \
     do {                                                                                                              \
         static std::atomic<unsigned long long> attr_set{0};                                                           \
         int dev_ = 0;                                                                                                 \
         (void)hipGetDevice(&dev_);                                                                                    \
         if (!((attr_set.load(std::memory_order_acquire) >> (dev_ & 63)) & 1ull)) {                                     \
-            hipError_t e = hipFuncSetAttribute((const void *)k_first_layer_gather<ACT, WAVES, C>,                     \
+            hipError_t e = hipFuncSetAttribute((const void *)k_first_layer_gather<ACT, WAVES, C, MAP>,                \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);           \
             if (e != hipSuccess) return hip_rc(e);                                                                    \
             attr_set.fetch_or(1ull << (dev_ & 63), std::memory_order_release);                                        \
         }                                                                                                             \
-        hipLaunchKernelGGL((k_first_layer_gather<ACT, WAVES, C>), grid, dim3(WAVES * kWave), lds_bytes, s, (const u8 *)soa, n, stride, \
-                           (const float4 *)w_rows, bias, (unsigned char *)out_hi_lo, (u32)H, rows_per_block, alpha, (int *)range_flag); \
+        hipLaunchKernelGGL((k_first_layer_gather<ACT, WAVES, C, MAP>), grid, dim3(WAVES * kWave), lds_bytes, s, (const u8 *)soa, n, stride, \
+                           (const float4 *)w_rows, bias, (unsigned char *)out_hi_lo, (u32)H, rows_per_block, alpha, (int *)range_flag,  \
+                           rows_dev, src_map);                                                                          \
     } while (0)
-#define RC_LAUNCH_GA_ACT(ACT)            \
-    do {                                 \
-        if (wide) RC_LAUNCH_GA(ACT, 8, 8); \
-        else RC_LAUNCH_GA(ACT, 16, 4);   \
+#define RC_LAUNCH_GA_ACT(ACT)                              \
+    do {                                                   \
+        if (rows_dev) {                                    \
+            if (wide) RC_LAUNCH_GA(ACT, 8, 8, true);       \
+            else RC_LAUNCH_GA(ACT, 16, 4, true);           \
+        } else if (wide) RC_LAUNCH_GA(ACT, 8, 8, false);   \
+        else RC_LAUNCH_GA(ACT, 16, 4, false);              \
     } while (0)
     if (activation == RC_ACT_ELU) RC_LAUNCH_GA_ACT(RC_ACT_ELU);
     else if (activation == RC_ACT_RELU) RC_LAUNCH_GA_ACT(RC_ACT_RELU);
@@ -1069,6 +1127,18 @@ extern "C" int rc_first_layer_gather_f16(const int8_t *soa, size_t n, size_t str
 #undef RC_LAUNCH_GA_ACT
 #undef RC_LAUNCH_GA
     return launch_status();
+}
+
+extern "C" int rc_first_layer_gather_f16(const int8_t *soa, size_t n, size_t stride, const float *w_rows, const float *bias,
+                                         uint16_t *out_hi_lo, size_t H, int activation, float alpha, int32_t *range_flag,
+                                         rc_stream_t stream) {
+    return first_layer_gather(soa, n, stride, w_rows, bias, out_hi_lo, H, activation, alpha, range_flag, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int rc_first_layer_gather_rows_f16(const int8_t *soa, size_t n, size_t stride, const float *w_rows, const float *bias,
+                                              uint16_t *out_hi_lo, size_t H, int activation, float alpha, int32_t *range_flag,
+                                              const uint32_t *rows_dev, const int32_t *src_map, int form, rc_stream_t stream) {
+    return first_layer_gather(soa, n, stride, w_rows, bias, out_hi_lo, H, activation, alpha, range_flag, rows_dev, src_map, form, stream);
 }
 
 extern "C" int rc_adi_targets(const float *values, const uint8_t *child_solved, const uint8_t *state_solved, size_t n,

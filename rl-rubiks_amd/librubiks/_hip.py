@@ -42,8 +42,10 @@ SIGNATURES = {
     "rc_first_layer_split_f16": [P, SZ, SZ, P, P, P, P, SZ, I, ctypes.c_float, P],
     "rc_first_layer_split_flag_f16": [P, SZ, SZ, P, P, P, P, SZ, I, ctypes.c_float, P, P],
     "rc_first_layer_gather_f16": [P, SZ, SZ, P, P, P, SZ, I, ctypes.c_float, P, P],
+    "rc_first_layer_gather_rows_f16": [P, SZ, SZ, P, P, P, SZ, I, ctypes.c_float, P, P, P, I, P],
     "rc_split_act_f16": [P, P, ctypes.c_float, SZ, SZ, P, I, ctypes.c_float, P, P, P],
     "rc_split_reduce_f16": [P, SZ, I, I, SZ, SZ, P, P, I, ctypes.c_float, P, P, P, P, P, P],
+    "rc_split_reduce_rows_f16": [P, SZ, I, I, SZ, SZ, P, P, I, ctypes.c_float, P, P, P, P, P, P, P],
     "rc_split_layer_f16": [P, P],
     "rc_gemm_layer_bf16": [P, P],
     "rc_split_layer_corr_chunks": [SZ, I],
@@ -52,6 +54,7 @@ SIGNATURES = {
     "rc_gemm_bias_act_bf16": [P, P, P, SZ, SZ, SZ, I, ctypes.c_float, P, I, P],
     "rc_split_gemm_partials_f16": [P, P, SZ, SZ, SZ, P, P],
     "rc_head_split_f32": [P, P, ctypes.c_float, SZ, SZ, P, I, ctypes.c_float, P, P, SZ, P, P],
+    "rc_head_split_rows_f32": [P, P, ctypes.c_float, SZ, SZ, P, I, ctypes.c_float, P, P, SZ, P, P, P, P],
     "rc_head_bf16": [P, SZ, SZ, P, P, SZ, P, I, ctypes.c_float, P],
     "rc_adi_targets": [P, P, P, SZ, SZ, ctypes.c_float, I, P, P, P],
     "rc_first_layer_mfma_bf16": [P, SZ, SZ, P, P, P, SZ, I, ctypes.c_float, I, P],

@@ -721,7 +721,7 @@ class _SplitLayer(ctypes.Structure):   # mirrors rc_split_layer_t (include/rubik
                                                "out_partials", "out_bf16")] + \
                [(n, ctypes.c_size_t) for n in ("n_rows", "n_out", "k")] + \
                [("activation", ctypes.c_int), ("alpha", ctypes.c_float), ("tile", ctypes.c_int), ("k_splits", ctypes.c_int),
-                ("range_flag", ctypes.c_void_p), ("products", ctypes.c_int)]
+                ("range_flag", ctypes.c_void_p), ("products", ctypes.c_int), ("rows_dev", ctypes.c_void_p)]
 
 
 def _ptr(t):
@@ -954,16 +954,20 @@ class SplitF32Net:
         oh = oh.float()
         return torch.cat([oh, oh * (1.0 / SPLIT_SCALE)], 1).half()   # exact: entries are 0, 1 and 2^-11
 
-    def _act(self, part: torch.Tensor, n_corr: int, bias: torch.Tensor, code: int, alpha: float, split: bool, skip=None, post=None) -> torch.Tensor:
+    def _act(self, part: torch.Tensor, n_corr: int, bias: torch.Tensor, code: int, alpha: float, split: bool, skip=None, post=None,
+             rows_dev=None) -> torch.Tensor:
         """post * act(sum of the partial products + bias + skip) + post' as [hi | lo] halves (split) or as fp32.  part: [P, n, w] fp32, the
-        first n_corr of them correction products (still scaled by 2^11); skip: [n, 2 w] halves hi | lo."""
+        first n_corr of them correction products (still scaled by 2^11); skip: [n, 2 w] halves hi | lo.  rows_dev: a device word, only
+        that many rows exist."""
         from librubiks import _hip
         P, n, w = part.shape
         out = torch.empty((n, 2 * w), dtype=torch.float16, device=part.device) if split else torch.empty((n, w), dtype=torch.float32, device=part.device)
-        _hip.check(_hip.lib().rc_split_reduce_f16(part.data_ptr(), n * w, P, n_corr, n, w, bias.data_ptr(), _ptr(skip), code, alpha,
-                                                  _ptr(post[0]) if post else None, _ptr(post[1]) if post else None,
-                                                  out.data_ptr() if split else None, None if split else out.data_ptr(),
-                                                  self.range_flag.data_ptr(), _hip.stream_ptr()), "rc_split_reduce_f16")
+        args = (part.data_ptr(), n * w, P, n_corr, n, w, bias.data_ptr(), _ptr(skip), code, alpha, _ptr(post[0]) if post else None,
+                _ptr(post[1]) if post else None, out.data_ptr() if split else None, None if split else out.data_ptr(), self.range_flag.data_ptr())
+        if rows_dev is None:
+            _hip.check(_hip.lib().rc_split_reduce_f16(*args, _hip.stream_ptr()), "rc_split_reduce_f16")
+        else:
+            _hip.check(_hip.lib().rc_split_reduce_rows_f16(*args, rows_dev.data_ptr(), _hip.stream_ptr()), "rc_split_reduce_rows_f16")
         return out
 
     def _zero_bias(self, w: int) -> torch.Tensor:
@@ -972,8 +976,9 @@ class SplitF32Net:
     fused_input = True   # the input layer as one kernel from the cube states when shapes allow ...
     gather_input = True  # ... rc_first_layer_gather_f16 (sum of 20 fp32 rows of W^T per state); False: rc_first_layer_split_f16 (one-hot MFMA, hi / lo tables)
 
-    def _first_from_cubes(self, cubes, layers, lo: int = 0, n: int = None):
-        """[hi | lo] activations of the input layer straight from device cubes, or None if the fused kernel does not apply."""
+    def _first_from_cubes(self, cubes, layers, lo: int = 0, n: int = None, pack=None):
+        """[hi | lo] activations of the input layer straight from device cubes, or None if the fused kernel does not apply.
+        pack = (rows_dev, src_map): output row r is the layer of state src_map[r], for r < rows_dev[0] only (`packs_rows`)."""
         from librubiks import _hip
         _, B, b, code, alpha, Wh, Wl, Wrows = layers[0][:8]
         H = Wh.shape[0]
@@ -984,6 +989,11 @@ class SplitF32Net:
             assert lo % 16 == 0 and 0 <= lo and lo + n <= cubes.n
             cubes = _CubeWindow(cubes.soa.data_ptr() + lo, n, cubes.stride)
         out = torch.empty((cubes.n, 2 * H), dtype=torch.float16, device=self.device)
+        if pack is not None:
+            _hip.check(_hip.lib().rc_first_layer_gather_rows_f16(_soa_ptr(cubes), cubes.n, cubes.stride, Wrows.data_ptr(), b.data_ptr(), out.data_ptr(),
+                                                                 H, code, alpha, self.range_flag.data_ptr(), pack[0].data_ptr(), pack[1].data_ptr(), 0,
+                                                                 _hip.stream_ptr()), "rc_first_layer_gather_rows_f16")
+            return out
         if self.gather_input:   # the one-hot row times W as the sum of 20 rows of W^T, in fp32 (no matrix cores: 20 additions per output)
             _hip.check(_hip.lib().rc_first_layer_gather_f16(_soa_ptr(cubes), cubes.n, cubes.stride, Wrows.data_ptr(), b.data_ptr(), out.data_ptr(), H,
                                                             code, alpha, self.range_flag.data_ptr(), _hip.stream_ptr()), "rc_first_layer_gather_f16")
@@ -993,12 +1003,30 @@ class SplitF32Net:
                    "rc_first_layer_split_flag_f16")
         return out
 
-    def _forward_cubes(self, cubes, layers, lo: int = 0, n: int = None) -> torch.Tensor:
-        a = self._first_from_cubes(cubes, layers, lo, n)
+    def _forward_cubes(self, cubes, layers, lo: int = 0, n: int = None, pack=None) -> torch.Tensor:
+        a = self._first_from_cubes(cubes, layers, lo, n, pack)
         src = _window(cubes, lo, n) if self._conv is not None else None
         if a is None:
             return self._forward(self._input_from_cubes(cubes, lo, n), layers, src=src)
-        return self._forward(a, layers, first=1, src=src)
+        return self._forward(a, layers, first=1, src=src, pack=pack)
+
+    def packs_rows(self, rows: int) -> bool:
+        """Whether `head_cubes` on `rows` states takes a device row count and a source-row map: the input layer runs as the sum of
+        rows, every hidden layer on the own kernel (whole K or cut), and the output layer in the fused head behind a K-cut layer
+        -- the forms that read the count on the device.  The plan is that of `rows`, whatever the count turns out to be."""
+        layers = self.layers
+        if self._conv is not None or not (self.fused_input and self.gather_input and self.fused_head) or len(layers) < 3:
+            return False
+        if layers[0][0] != "in" or layers[0][5].shape[0] % 64 or layers[-1][0] != "f32" or layers[-1][1].shape[0] > 16:
+            return False
+        for i in range(1, len(layers) - 1):
+            o = self._opts.get(id(layers[i])) or _PLAIN
+            if layers[i][0] != "hid" or o.cat:
+                return False
+            plan, last = self._layer_plan(rows, layers, i), i == len(layers) - 2
+            if plan == "library" or (last and (plan == "fused" or o.add or o.post or layers[i][1].shape[0] not in (512, 1024))):
+                return False
+        return True
 
     def _with_conv(self, a: torch.Tensor, src) -> torch.Tensor:
         """[hi | lo] of [x | conv branch of the same states]: rc_conv686_branch writes its two blocks of the wide operand in place
@@ -1014,11 +1042,14 @@ class SplitF32Net:
         return buf
 
     @torch.no_grad()
-    def _forward(self, a: torch.Tensor, layers, first: int = 0, src=None) -> torch.Tensor:
+    def _forward(self, a: torch.Tensor, layers, first: int = 0, src=None, pack=None) -> torch.Tensor:
         """a: [n, 960] half operand of the input layer (or, with first = 1, its [hi | lo] output) -> fp32 [n, n_out].  src: the cube
-        states (or one-hot batch) behind `a`, for a network with a conv branch."""
+        states (or one-hot batch) behind `a`, for a network with a conv branch.  pack = (rows_dev, src_map): only the first
+        rows_dev[0] rows of `a` exist (device word); the head writes row r's outputs to row src_map[r] and no other row (`packs_rows`)."""
         from librubiks import _hip
         skip = None
+        rows_dev = None if pack is None else pack[0]
+        assert pack is None or (first == 1 and self.packs_rows(a.shape[0])), "this network / launch size does not take packed rows"
         for i, layer in enumerate(layers):
             if i < first:
                 continue
@@ -1046,7 +1077,7 @@ class SplitF32Net:
                     _layer_call("rc_split_layer_f16", a=a, w=W3, bias=b, residual=res, post_scale=post[0] if post else None,
                                 post_shift=post[1] if post else None, n_rows=n, n_out=w, k=K, activation=code, alpha=alpha,
                                 out_hi_lo=None if last_hidden else out, out_f32=out if last_hidden else None,
-                                tile=self._fused_tile(n, w, K), k_splits=1, range_flag=self.range_flag)
+                                tile=self._fused_tile(n, w, K), k_splits=1, range_flag=self.range_flag, rows_dev=rows_dev)
                     a = out
                     continue
                 nxt = layers[i + 1]
@@ -1061,7 +1092,7 @@ class SplitF32Net:
                     # chunk, ~one per CU), raw fp32 partials; the first n_corr hold correction products only (still scaled by 2^11)
                     _, tile, chunks = plan
                     part = torch.empty((chunks, n, w), dtype=torch.float32, device=a.device)
-                    _layer_call("rc_split_layer_f16", a=a, w=W3, n_rows=n, n_out=w, k=K, out_partials=part, k_splits=chunks, tile=tile)
+                    _layer_call("rc_split_layer_f16", a=a, w=W3, n_rows=n, n_out=w, k=K, out_partials=part, k_splits=chunks, tile=tile, rows_dev=rows_dev)
                     n_corr = _hip.lib().rc_split_layer_corr_chunks(K, chunks)
                 if head_ok:
                     # activation + the skinny output layer in one pass: the fp32 activations are never written (rc_head_split_f32)
@@ -1069,15 +1100,19 @@ class SplitF32Net:
                     if part.shape[0] == 2 and n_corr == 1:
                         c, c_corr, bias_h, act_h = part[1], part[0], b, code
                     else:   # more than two partials: summed (bias, activation) by the reduce kernel first
-                        c, c_corr, bias_h, act_h = self._act(part, n_corr, b, code, alpha, split=False), None, self._zero_bias(w), 0
-                    _hip.check(_hip.lib().rc_head_split_f32(c.data_ptr(), _ptr(c_corr), 1.0 / SPLIT_SCALE, n, w, bias_h.data_ptr(), act_h, alpha,
-                                                            nxt[1].data_ptr(), nxt[2].data_ptr(), nxt[1].shape[0], out.data_ptr(),
-                                                            _hip.stream_ptr()), "rc_head_split_f32")
+                        c, c_corr, bias_h, act_h = self._act(part, n_corr, b, code, alpha, split=False, rows_dev=rows_dev), None, self._zero_bias(w), 0
+                    args = (c.data_ptr(), _ptr(c_corr), 1.0 / SPLIT_SCALE, n, w, bias_h.data_ptr(), act_h, alpha, nxt[1].data_ptr(), nxt[2].data_ptr(),
+                            nxt[1].shape[0], out.data_ptr())
+                    if pack is None:
+                        _hip.check(_hip.lib().rc_head_split_f32(*args, _hip.stream_ptr()), "rc_head_split_f32")
+                    else:   # row r's outputs to the row slot it came from; slots without a state keep what they held
+                        _hip.check(_hip.lib().rc_head_split_rows_f32(*args, pack[0].data_ptr(), pack[1].data_ptr(), _hip.stream_ptr()),
+                                   "rc_head_split_rows_f32")
                     return out[:, :nxt[1].shape[0]]
             else:
                 _, W, b = layer
                 return torch.addmm(b, a, W.t())
-            a = self._act(part, n_corr, b, code, alpha, split=not last_hidden, skip=res, post=post)   # the output layer takes plain fp32 activations
+            a = self._act(part, n_corr, b, code, alpha, split=not last_hidden, skip=res, post=post, rows_dev=rows_dev)   # the output layer takes plain fp32 activations
         return a
 
     # ---- InferenceNet's interface --------------------------------------------------------------------------------
@@ -1105,9 +1140,11 @@ class SplitF32Net:
         return self._forward(self._input_from_oh(oh), self.value_layers, src=oh).reshape(-1)
 
     @torch.no_grad()
-    def head_cubes(self, cubes, x1=None) -> torch.Tensor:
-        """[n, 13] float32: 12 policy logits, then the value (the layout rc_mcts_backup_head reads)."""
-        return self._forward_cubes(cubes, self.layers)
+    def head_cubes(self, cubes, x1=None, rows_dev=None, src_map=None) -> torch.Tensor:
+        """[n, 13] float32: 12 policy logits, then the value (the layout rc_mcts_backup_head reads).
+        rows_dev, src_map (device int32, both or neither; `packs_rows`): the network runs on rows_dev[0] packed rows, row r being state
+        src_map[r] of `cubes`, and writes r's outputs to row src_map[r]: those rows hold the bits of the plain call, the others nothing."""
+        return self._forward_cubes(cubes, self.layers, pack=None if rows_dev is None else (rows_dev, src_map))
 
     @torch.no_grad()
     def forward_cubes(self, cubes, x1=None):

@@ -56,6 +56,7 @@ _hip.register({
     "rc_mcts_plant_expanded": [POINTER(_McStruct), c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_uint32, c_void_p],
     "rc_mcts_step": [POINTER(_McStruct), c_void_p, c_void_p, c_double, c_uint32, c_uint32, c_void_p],
     "rc_mcts_step_head": [POINTER(_McStruct), c_void_p, c_size_t, c_int, c_double, c_uint32, c_uint32, c_void_p],
+    "rc_mcts_row_map": [POINTER(_McStruct), c_void_p, c_void_p, c_void_p, c_void_p],
     "rc_mcts_complete_graph": [POINTER(_McStruct), c_void_p],
     "rc_mcts_shorten": [POINTER(_McStruct), c_void_p],
     "rc_mcts_copy_trees": [POINTER(_McStruct), POINTER(_McStruct), c_void_p, c_uint32, c_uint32, c_void_p],
@@ -295,6 +296,11 @@ class MCTSForest:
         self.child_idx = z((B, N_ACT), torch.int32)
         self.new_mask = z((B,), torch.int32)
         self.expanded = z((B,), torch.uint8)
+        # the packed rows of a one-launch step (`pack_rows`): their number R, the first packed row of every list position, the row
+        # slot behind every packed row -- device words (rc_mcts_row_map), static like every buffer a captured graph names
+        self.row_count = z((4,), torch.int32)
+        self.row_first = z((B,), torch.int32)
+        self.row_src = z((ROWS * B,), torch.int32)
         self.probs = z((ROWS * B, N_ACT), torch.float32)     # static network outputs (graph capture)
         self.values = z((ROWS * B,), torch.float32)
         s = _McStruct()
@@ -328,7 +334,8 @@ class MCTSForest:
         self.engine = None
         self._net_fp = None
         self._oh = None
-        self._graphs = {}          # (G, c, max_states, level budget) -> captured iteration
+        self._graphs = {}          # (G, c, max_states, level budget, form) -> captured iteration
+        self._packs = {}           # G -> whether the engine takes packed rows at that launch size (`_packing`)
         self._graph_pool = None    # one memory pool for all of them: they never run concurrently
 
     @classmethod
@@ -670,6 +677,7 @@ class MCTSForest:
         else:
             self._oh = torch.empty((ROWS * self.B, getattr(self.engine, "input_width", 480)), dtype=self.engine.input_dtype, device=self.device)
         self._graphs = {}
+        self._packs = {}
         self._graph_pool = None   # (a pool whose graphs have all been dropped cannot be captured into again: a fresh one next time)
 
     rows_per_tree = ROWS
@@ -730,6 +738,30 @@ class MCTSForest:
                                           roots.soa.data_ptr(), roots.stride, first, _hip.stream_ptr()), "rc_mcts_plant")
 
     level_budget = 0   # new levels a tree may descend per iteration (0 = unlimited, strict lock step)
+    # One-launch steps on an engine that takes a device row count (SplitF32Net.packs_rows): the network runs on the rows that hold a
+    # state -- a tree fills as many of its 11 row slots as its expansion made new nodes, 0.92 of them in a full forest -- packed in
+    # list order (rc_mcts_row_map), and the head writes each output to its row slot.  Same bits per node (a row's outputs do not
+    # depend on the other rows of a launch), fewer rows through every network kernel.  False: every row slot is evaluated.
+    pack_rows = True
+
+    def _packing(self) -> bool:
+        """Whether this forest's next one-launch step packs its network rows."""
+        if not (self.pack_rows and self._one_launch and self._fused):
+            return False
+        ok = self._packs.get(self.G)
+        if ok is None:   # the engine's answer for this launch size, asked once (`set_net` forgets it)
+            packs = getattr(self.engine, "packs_rows", None)
+            ok = self._packs[self.G] = bool(packs is not None and packs(ROWS * self.G))
+        return ok
+
+    def row_map(self):
+        """rc_mcts_row_map on the listed trees as they are: (row_count, row_first, row_src) device tensors, stream-ordered."""
+        _hip.check(self.lib.rc_mcts_row_map(ctypes.byref(self.struct), self.row_count.data_ptr(), self.row_first.data_ptr(),
+                                            self.row_src.data_ptr(), _hip.stream_ptr()), "rc_mcts_row_map")
+        return self.row_count, self.row_first, self.row_src
+
+    def _graph_key(self, c: float, max_states: int):
+        return (self.G, float(c), int(max_states), int(self.level_budget), (self._one_launch, self._packing()))   # the form of the iteration
 
     def _iteration(self, c: float, max_states: int):
         st = _hip.stream_ptr()
@@ -737,7 +769,13 @@ class MCTSForest:
         if self._one_launch:   # the rows were left by the previous step's expansion (or by the plant): network, then ONE tree kernel
             if self._fused:
                 cubes, rows = self._net_input()
-                head = self.engine.head_cubes(cubes, None if self._x1 is None else self._x1[:rows])
+                if self._packing():
+                    # the counts are read off the listed trees (expanded, phase, new_mask -- what the backup reads its rows by), so
+                    # they follow a tree through `set_active` and a plant by themselves
+                    self.row_map()
+                    head = self.engine.head_cubes(cubes, None if self._x1 is None else self._x1[:rows], self.row_count, self.row_src)
+                else:
+                    head = self.engine.head_cubes(cubes, None if self._x1 is None else self._x1[:rows])
                 _hip.check(self.lib.rc_mcts_step_head(m, head.data_ptr(), head.stride(0), int(head.dtype == torch.bfloat16), c,
                                                       self.level_budget, max_states, st), "rc_mcts_step_head")
             else:
@@ -785,7 +823,7 @@ class MCTSForest:
             self._steps_covered -= 1
         if not use_graph:
             return self._iteration(c, max_states)
-        key = (self.G, float(c), int(max_states), int(self.level_budget), self._one_launch)
+        key = self._graph_key(c, max_states)
         g = self._graphs.get(key)
         if g is None:
             # this call's iteration runs eagerly (hipBLASLt picks its kernels, the allocator settles);
@@ -807,7 +845,7 @@ class MCTSForest:
     def _graph_of_steps(self, c: float, max_states: int):
         """The HIP graph of GRAPH_STEPS consecutive iterations at the current launch size (captured on first use, once the
         one-iteration graph of that size exists: its eager run has settled the library's kernel choices and the allocator)."""
-        key = (self.G, float(c), int(max_states), int(self.level_budget), self._one_launch)
+        key = self._graph_key(c, max_states)
         if key not in self._graphs:
             return None
         g = self._graphs.get(key + (self.GRAPH_STEPS,))
@@ -849,7 +887,7 @@ class MCTSForest:
         self._one_launch = bool(self.fused_step)
         for G in self.rungs:
             self.set_active(np.arange(G))
-            if (self.G, float(c), int(max_states), int(self.level_budget), self._one_launch) not in self._graphs:
+            if self._graph_key(c, max_states) not in self._graphs:
                 self.step(c, max_states, use_graph=True)
             if self.GRAPH_STEPS > 1:
                 self._graph_of_steps(c, max_states)

@@ -2,10 +2,11 @@
 The hidden-layer kernel of the split network (rc_split_layer_f16) by tile, row count and operand data, against the library's
 bf16 GEMM of the same shape as the yardstick:
 
-    python tools/gemm_tile_ab.py [--rows 11264,196608,524288] [--tiles 1,4,6] [--k 4096] [--n 2048] [--reps 10] [--out f.json]
+    python tools/gemm_tile_ab.py [--rows 11264,196608,524288] [--tiles 1,4,6] [--packed 10240,10336] [--k 4096] [--n 2048] [--reps 10] [--out f.json]
 
 Per (rows, tile): milliseconds (HIP events over `reps` launches), TFLOP/s of executed f16 flops (3 products), fraction of the
 2.5 PFLOP/s dense f16 peak, and whether the output equals tile 1's bit for bit (every tile walks K in the same order).
+`--packed R,...`: tile 1 with a device row count R (the packed rows of an MCTS step): ms, and whether rows < R equal the plain launch's.
 `hipblaslt_bf16`: torch.mm of [rows, k] x [k, n] bf16 (one product): what the library reaches on this box in this run.
 RUBIKS_HIP_LIB selects another build of the library (tools/build_ab_lib.sh): the same command under two builds is the A/B.
 """
@@ -43,6 +44,7 @@ def main():
     ap.add_argument("--n", type=int, default=2048)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--data", default="elu", choices=["elu", "zeros"], help="elu: ELU(N(0,1)) activations and N(0,1/sqrt k) weights, split exactly")
+    ap.add_argument("--packed", default="", help="row counts R: tile 1 with a device row count, e.g. 10240,10336,10752,11264")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -87,6 +89,20 @@ def main():
             checksum = int((v * (torch.arange(v.numel(), device=dev, dtype=torch.int64) % 8191 + 1)).sum().item()) & ((1 << 62) - 1)   # equal across builds <=> same bits
             rec = {"rows": M, "tile": tile, "ms": round(ms, 4), "tflops_f16": round(flops / ms / 1e9, 1), "frac": round(flops / ms / 1e9 / PEAK, 4),
                    "bit_identical_to_first_tile": same, "checksum": checksum}
+            print(json.dumps(rec), flush=True)
+            out["runs"].append(rec)
+        # --packed: the 352 x 256 tile with a device row count R (rc_split_layer_t::rows_dev): the same grid, every row tile an even
+        # share of the R rows in whole 16-row fragments.  R = M is the packed kernel's own cost against tile 1 above.
+        for R in (int(v) for v in args.packed.split(",") if v):
+            from librubiks.model import _layer_call
+            word = torch.tensor([R, 0, 0, 0], dtype=torch.int32, device=dev)
+            y.zero_()
+            run = lambda: _layer_call("rc_split_layer_f16", a=a, w=W3, bias=bias, n_rows=M, n_out=N, k=K, activation=2, alpha=1.0, out_hi_lo=y,   # noqa: E731
+                                      tile=1, k_splits=1, rows_dev=word)
+            ms = timed(run, args.reps)
+            tiles = -(-M // 352)
+            rec = {"rows": M, "tile": "1_packed", "R": R, "tile_height": min(352, 16 * -(-R // (16 * tiles))), "ms": round(ms, 4),
+                   "bit_identical_to_first_tile": None if first is None else bool(torch.equal(first[:R], y[:R]))}
             print(json.dumps(rec), flush=True)
             out["runs"].append(rec)
         del first
