@@ -800,6 +800,80 @@ int rc_bfs_commit(const rc_bfs_t *b, uint32_t lo, uint32_t n_parents, uint32_t n
 int rc_bfs_path(const rc_bfs_t *b, uint32_t node, uint8_t *out_actions, uint32_t *out_len, uint32_t max_len,
                 rc_stream_t stream);
 
+/* ---- batched breadth-first search: S problems advanced in lock step (csrc/rubiks_bfs_batch.hip) ------
+ *
+ * Replaces the FIFO loop of librubiks/solving/agents.py:92-129 for S games at once, with the bookkeeping of rc_bfs_* above kept
+ * per slot and the decision rc_bfs_* leaves to the host after every chunk (commit, stop, path) made on the device.  A slot owns
+ * `capacity` node rows (16-byte packed key, parent, action; node indices are per slot and 32-bit), `hash_size` hash cells and a
+ * segment of 12 * chunk child rows: row 12 * chunk * s + 12 p + k = action k on the p-th parent of slot s's chunk.  Rows beyond
+ * 12 * n_par of a slot are dead.  Offsets of a slot's arrays inside the batch arrays are size_t.
+ * words[w * n_slots + s] is word w of slot s (RC_BFSB_W_*): what the host reads per round are the first RC_BFSB_HOST_WORDS rows.
+ * Device pointers; nothing needs initialising except that every status starts RC_BFSB_EMPTY; games enter through
+ * rc_bfs_batch_plant.  Launch boundaries are the only synchronisation between workgroups.
+ */
+#define RC_BFSB_RUNNING 0
+#define RC_BFSB_SOLVED 1        /* the first solved row lies before the cut (agents.py:111-116) */
+#define RC_BFSB_CUT 2           /* len(self) >= max_states before a pop (agents.py:105) */
+#define RC_BFSB_FAILED 3        /* a word or an index read from memory was out of range, or the parent chain is longer than the queue row */
+#define RC_BFSB_ROOT_SOLVED 4   /* agents.py:100 */
+#define RC_BFSB_GRAPH_DONE 5    /* a whole level brought nothing new (the reference would pop from an empty deque) */
+#define RC_BFSB_EMPTY 6         /* no game in the slot */
+
+#define RC_BFSB_W_STATUS 0
+#define RC_BFSB_W_NODES 1       /* len(agent) */
+#define RC_BFSB_W_LEVELS 2
+#define RC_BFSB_W_QUEUE_LEN 3   /* -1 while a solved slot's path is not written yet */
+#define RC_BFSB_W_LO 4          /* frontier = nodes lo .. level_end - 1 */
+#define RC_BFSB_W_LEVEL_END 5
+#define RC_BFSB_W_MAX_STATES 6
+#define RC_BFSB_HOST_WORDS 7
+#define RC_BFSB_W_N_PAR 7       /* parents of the next chunk (0: the slot does nothing) */
+#define RC_BFSB_W_FIRST_SOLVED 8 /* lowest solved local row of the chunk, ~0 = none */
+#define RC_BFSB_W_C_ROWS 9      /* the commit the last decision allows: its rows (0 = none), */
+#define RC_BFSB_W_C_BASE 10     /*   the node count before it */
+#define RC_BFSB_W_C_LO 11       /*   and the first parent of its chunk */
+#define RC_BFSB_W_SOLVED_PARENT 12
+#define RC_BFSB_W_LAST_ACTION 13
+#define RC_BFSB_WORDS 14
+
+typedef struct rc_bfs_batch {
+    uint32_t n_slots;     /* S */
+    uint32_t chunk;       /* C: most parents of a slot per step; S * 12 * C < 2^31 */
+    uint32_t capacity;    /* node rows per slot >= 12 * C + 2: max_states of a slot is at most capacity - 12 * C - 1 */
+    uint32_t hash_size;   /* hash cells per slot: power of two, >= 2 * capacity */
+    uint32_t queue_width; /* bytes per queue row */
+    uint32_t reserved;
+    void *keys;           /* [S][capacity] uint32[4] packed state per node (as rc_bfs) */
+    uint32_t *parent;     /* [S][capacity] */
+    uint8_t *action;      /* [S][capacity] */
+    int32_t *hash;        /* [S][hash_size]: > 0 node index + 1, < 0 pending local row -(row+1), 0 empty */
+    void *child_keys;     /* [S * 12 * C] uint32[4] */
+    int32_t *child_slot;  /* [S * 12 * C] */
+    uint32_t *flags;      /* [S * 12 * C] 1 = new state; 0 on dead rows */
+    uint32_t *prefix;     /* [S * 12 * C] exclusive prefix sum of flags over the whole row space */
+    int64_t *words;       /* [RC_BFSB_WORDS][S] */
+    uint8_t *queues;      /* [S][queue_width] actions from the root to the solution */
+    void *scan_tmp;       /* rc_bfs_batch_scan_bytes(S, C) bytes */
+    size_t scan_tmp_bytes;
+} rc_bfs_batch_t;
+
+size_t rc_bfs_batch_struct_bytes(void);
+size_t rc_bfs_batch_scan_bytes(uint32_t n_slots, uint32_t chunk);
+/* agents.py:92-103 (`search` up to its loop) for the listed slots: slot slots[i] (int32 [n], device; entries < 0 or >= S are
+ * skipped) restarts from column first_col + i of roots_soa (20 code planes, as rc_egvm_plant) with max_states[i] (uint32 [n],
+ * device; clamped to what the slot's node rows hold).  Clears the slot's hash cells, stores the root as node 0 and resets the
+ * slot's words; the solved cube ends at once, RC_BFSB_ROOT_SOLVED with 0 nodes (agents.py:100).  A former tenant's node rows
+ * above the new node count are never read.  A slot may be listed once. */
+int rc_bfs_batch_plant(const rc_bfs_batch_t *b, const int32_t *slots, uint32_t n, const int8_t *roots_soa, size_t stride,
+                       size_t first_col, const uint32_t *max_states, rc_stream_t stream);
+/* agents.py:104-129 for the next chunk (at most C parents) of every running slot, without a host read: children and table
+ * lookup, claims (the lowest row of a state wins within its slot), flags, one exclusive scan over the row space, the per-slot
+ * decision -- solved before the cut (agents.py:111-116: nodes += new rows before it), cut inside the chunk (agents.py:105:
+ * nodes += new rows before the cut parent), else commit and advance (at a level's end level_end = nodes, levels += 1; nothing new
+ * in a whole level: RC_BFSB_GRAPH_DONE), then the test of agents.py:105 for the next chunk --, the gated commit, and the path of
+ * the slots that have just solved (agents.py:112-115), root first, into their queue rows.  Finished and empty slots do nothing. */
+int rc_bfs_batch_step(const rc_bfs_batch_t *b, rc_stream_t stream);
+
 /* ---- the 6x8x6 representation (csrc/rubiks_env686.hip) -------------------------------------------------------------
  * The reference's second representation (librubiks/cube/cube.py:67-71,311-388): a state is int8[6][8][6], the one-hot colour of
  * the 8 non-centre stickers of each face.  Device form: 48 int8 planes of sticker colour 0..5, plane f*8+p = sticker p of face f

@@ -22,6 +22,7 @@ from librubiks import _hip, gpu, no_grad
 from librubiks.cube.device import DeviceCubes, encode
 from librubiks.model import F32_SPLIT, F32_SPLIT_DET, Model, net_fingerprint
 from librubiks.solving import astar_device as ad
+from librubiks.solving import bfs_batch_device as bb
 from librubiks.solving import bfs_device as bd
 from librubiks.solving import egvm_device as ed
 from librubiks.solving import mcts_device as md
@@ -51,6 +52,7 @@ def time_only_capacity(n_trees: int) -> int:
         return DEFAULT_NODE_CAP
     return int(max(DEFAULT_NODE_CAP, min(md.MAX_CAPACITY, TIME_ONLY_HASH_BYTES // (8 * max(1, int(n_trees))) - 1)))
 bd_MAX_STATES = 1 << 26      # BFS bounded by time only: node slots for 2^26 states (~4 GB)
+BFS_BATCH_BYTES = 32 << 30   # pooled BFS: what the slots' node rows, hash tables and child rows (allocated up front) may take
 
 
 class Agent:
@@ -123,13 +125,16 @@ class BFS(Agent):
     """
     Breadth-first search (reference agents.py:92-131) with whole levels expanded on the GPU; solution,
     `len(agent)` and the stop rule are those of the reference's FIFO loop (csrc/rubiks_bfs.hip).
-    `time_limit` is tested between launch sequences instead of before every pop.
+    `time_limit` is tested between launch sequences instead of before every pop.  `search_batch(..., slots=S)` searches a
+    pool of games together, one game per slot (csrc/rubiks_bfs_batch.hip); `chunk` is a speed knob in both forms.
     """
 
-    def __init__(self, chunk: int = None):
+    def __init__(self, chunk: int = None, steps_per_round: int = 4):
         super().__init__()
         self.chunk = chunk
+        self.steps_per_round = int(steps_per_round)   # pooled form: steps between two looks at the slots' words (4: profiles/bfs_batch_probe.txt)
         self._dev = None
+        self._pool = None
 
     def _device_for(self, max_states: int) -> bd.BFSDevice:
         cap = int(min(max_states, bd_MAX_STATES))
@@ -148,8 +153,21 @@ class BFS(Agent):
         self.action_queue = deque(actions)
         return solved
 
-    def search_batch(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
-        """One search after the other (each one fills the GPU by itself); same result layout as the deep agents."""
+    def search_batch(self, states, time_limit: float = None, max_states: int = None, slots: int = None) -> BatchResult:
+        """
+        With slots=None: one search after the other (each one fills the GPU by itself); same result layout as the deep agents.
+        slots: search at most this many games at a time, all advancing together on the device, chunk by chunk
+        (librubiks/solving/bfs_batch_device.py); finished games hand their slots to the scrambles still waiting (continuous
+        batching, as `AStar.search_batch`).  Every game ends exactly -- solved flag, len(agent), action queue, status -- as its
+        own `search` does, whoever shares the batch, however many slots there are and whatever the chunk.  A round is
+        `steps_per_round` steps and one look at the slots' words; the clock is looked at between rounds only, and `time_limit`
+        bounds the whole pool.  Games that never got a slot before the time limit end unsolved, with 0 nodes, status EXHAUSTED
+        and 0 seconds.  The number of slots is bounded by BFS_BATCH_BYTES of per-slot arrays (`bfs_batch_plan`).
+        `BatchResult.iterations` is the number of levels per game, `game_seconds` the pool's per-game intervals.
+        """
+        if slots is not None:
+            time_limit, max_states = self.reset(time_limit, max_states)
+            return self._search_pool(DeviceCubes.of(states), time_limit, max_states, slots)
         states = states.numpy() if isinstance(states, DeviceCubes) else np.asarray(states)
         B = len(states)
         solved, lengths, nodes = np.zeros(B, dtype=bool), np.full(B, -1, dtype=np.int64), np.zeros(B, dtype=np.int64)
@@ -166,6 +184,72 @@ class BFS(Agent):
                 lengths[g] = len(self.action_queue)
         status = np.where(solved, np.where(nodes == 0, 4, 1), 2)
         return BatchResult(solved, lengths, nodes, QueueTable.from_queues(queues), tt.tock(), levels, status, each)
+
+    def _pool_for(self, n_slots: int, max_states: int, chunk: int) -> bb.BFSBatch:
+        b = self._pool
+        if b is None or (b.S, b.C) != (n_slots, chunk) or b.max_states < max_states or b.max_states > 4 * max_states:
+            self._pool = None   # frees the old buffers first
+            torch.cuda.empty_cache()
+            b = self._pool = bb.BFSBatch(n_slots, max_states, chunk)
+        return b
+
+    def _search_pool(self, roots: DeviceCubes, time_limit: float, max_states: int, slots) -> BatchResult:
+        """`search_batch(slots=...)` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit not given)."""
+        S, C, _, _, _ = bb.bfs_batch_plan(roots.n, max_states, slots, self.chunk)
+        cap = int(min(max_states, bd_MAX_STATES))
+        pool = SlotPool(roots.n, S, self.tt.tock)
+        S, owner = pool.S, pool.owner
+        batch = self._pool_for(S, cap, C)
+        caps = np.full(S, cap, dtype=np.int64)
+
+        def plant(into, first):
+            batch.plant(into, roots, first, caps[:len(into)])
+        self.tt.tick()
+        plant(np.arange(S), 0)                            # the first S scrambles; the others move in as games finish
+        host, ev = batch.snapshot()
+        ev.synchronize()
+        final = host.numpy().copy()
+        taken = []
+        while self.tt.tock() < time_limit:                # (the reference tests the clock before every pop, agents.py:105)
+            live = owner >= 0
+            ended = live & (final[bb.W_STATUS] != bb.RUNNING)
+            done = np.flatnonzero(ended)
+            pool.sighted(done, self.tt.tock())
+            if not (live & ~ended).any() and not pool.waiting:
+                break
+            if pool.waiting and len(done):
+                # the finished slots' results leave without waiting, then the waiting scrambles are planted there
+                w = final[:, done].copy()
+                taken.append((owner[done].copy(), w, batch.take_queues(done, w[bb.W_QUEUE_LEN].max())))
+                pool.refill(done, plant)
+            batch.step(self.steps_per_round)
+            host, ev = batch.snapshot()
+            ev.synchronize()
+            final = host.numpy().copy()
+            bb.check_words(final, batch.capacity)
+        seconds = self.tt.tock()
+        left = np.flatnonzero(owner >= 0)
+        pool.sighted(left[final[bb.W_STATUS, left] != bb.RUNNING], seconds)
+        parts = [(games, self._part(w, q[0], q[1])) for games, w, q in taken]
+        if len(left):
+            w = final[:, left]
+            parts.append((owner[left], self._part(w, *batch.take_queues(left, w[bb.W_QUEUE_LEN].max())[:2])))
+        result = BatchResult.merge(pool.n_games, parts, seconds)
+        pool.close(result, seconds, 2)
+        self._explored_states = int(result.nodes[0])
+        self.action_queue = result.queues[0]
+        return result
+
+    @staticmethod
+    def _part(words: np.ndarray, host: torch.Tensor, ev) -> BatchResult:
+        """Slots' words and queue rows as the serial form reports them: a cut, an exhausted graph and a game the time limit
+        stopped are all status 2 there."""
+        ev.synchronize()
+        status, nodes, levels, qlen = words[bb.W_STATUS], words[bb.W_NODES], words[bb.W_LEVELS], words[bb.W_QUEUE_LEN]
+        solved = (status == bb.SOLVED) | (status == bb.ROOT_SOLVED)
+        qlen = np.where(solved, qlen, 0)
+        return BatchResult(solved, np.where(solved, qlen, -1), nodes.copy(), QueueTable(host.numpy().copy(), qlen), 0.0, levels.copy(),
+                           np.where(solved, status, 2))
 
     def __str__(self):
         return "Breadth-first search"

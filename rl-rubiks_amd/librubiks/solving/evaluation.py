@@ -36,7 +36,7 @@ def _world_size() -> int:
 class Evaluator:
     def __init__(self, n_games, scrambling_depths, max_time=None, max_states=None, logger=NullLogger(), slots: int = None):
         """
-        slots: for agents whose `search_batch` takes `slots` (MCTS, AStar, EGVM, RandomSearch, PolicySearch, ValueSearch): the
+        slots: for agents whose `search_batch` takes `slots` (BFS, MCTS, AStar, EGVM, RandomSearch, PolicySearch, ValueSearch): the
         games of ALL depths form one pool that is searched with at most `slots` concurrent trees / A* problems / games, finished
         ones handing their place to waiting games (continuous batching); `max_time`, if given, then bounds the whole pool at
         max_time x len(depths).  Agents that draw random numbers then give every game a stream of its own, seeded by one
