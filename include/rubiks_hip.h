@@ -595,6 +595,20 @@ int rc_astar_gather_new(const rc_astar_t *a, const int32_t *new_offset, int8_t *
  * (agents.py:326-328,333-367).  values[new_offset[b] + i] belongs to new state i of problem b. */
 int rc_astar_push_relax(const rc_astar_t *a, const int32_t *new_offset, const float *values, double lambda,
                         rc_stream_t stream);
+/* The two phases above with N and lambda per problem, for batches whose problems are searched under different settings (a grid
+ * of (lambda, expansions) points as one pool: the reference's GridSearch, librubiks/solving/hyper_optim.py:94-111, runs one
+ * agent per point).  expansions[b] and lambda[b] are device arrays of n_problems entries: problem b's own N (agents.py:218)
+ * and lambda (agents.py:380-383).  Here a->expansions is the row stride of the per-iteration staging -- popped is
+ * [B][a->expansions], child_* and row_* are [B][12 a->expansions], as above -- and the upper bound of every expansions[b].
+ * rc_astar_pop_expand_each: problem b is exhausted when n + 12 expansions[b] > max_states (agents.py:236) or > capacity, and
+ * pops min(len(open), expansions[b]) nodes (agents.py:238).  expansions[b] is read clamped to 0 .. a->expansions, so no value
+ * leads outside the problem's own staging rows; a clamped 0 pops nothing and ends the problem as RC_ASTAR_OPEN_EMPTY.
+ * rc_astar_push_relax_each: cost = lambda[b] * G - value in float64, product and sum rounded separately (agents.py:383).
+ * Everything else is what rc_astar_pop_expand / rc_astar_push_relax do: a batch whose arrays all hold a->expansions and one
+ * lambda evolves exactly as under those. */
+int rc_astar_pop_expand_each(const rc_astar_t *a, uint32_t max_states, const int32_t *expansions, rc_stream_t stream);
+int rc_astar_push_relax_each(const rc_astar_t *a, const int32_t *new_offset, const float *values, const double *lambda,
+                             rc_stream_t stream);
 /* Restarts listed problem slots of a running batch: for i < n, slot slots[i] (device int32 list) gets roots_soa column
  * first_col + i as its root -- its hash row is cleared, then it holds exactly what rc_astar_init writes for a problem (node 1,
  * G 0, open list (0, 1), counters, status incl. RC_ASTAR_ROOT_SOLVED, solved_idx -1).  A listed index outside

@@ -143,7 +143,10 @@ __global__ __launch_bounds__(kBlock) void k_astar_plant(rc_astar_t a, const int 
 }
 
 // ---- pop + expand + dedup + append (agents.py:236-313) --------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_astar_pop_expand(rc_astar_t a, u32 max_states) {
+// kEach: problem b expands each[b] nodes an iteration (clamped to 0 .. a.expansions, which stays the row stride of the staging);
+// otherwise every problem expands a.expansions and `each` is not read.
+template <bool kEach>
+__global__ __launch_bounds__(kBlock) void k_astar_pop_expand(rc_astar_t a, u32 max_states, const int *__restrict__ each) {
     __shared__ u32 s_lut[sizeof(kTables.lut) / 4];
     __shared__ int s_scan[kBlock];
     __shared__ int s_npop, s_base;
@@ -157,11 +160,12 @@ __global__ __launch_bounds__(kBlock) void k_astar_pop_expand(rc_astar_t a, u32 m
         int npop = 0;
         if (a.status[b] == RC_ASTAR_RUNNING) {
             const u32 n = (u32)a.n_nodes[b];
-            if (n + a.expansions * kA12 > max_states || n + a.expansions * kA12 > a.capacity) {   // agents.py:236
+            const u32 nexp = kEach ? (u32)min(max(each[b], 0), (int)a.expansions) : a.expansions;
+            if (n + nexp * kA12 > max_states || n + nexp * kA12 > a.capacity) {   // agents.py:236
                 a.status[b] = RC_ASTAR_EXHAUSTED;
             } else {
                 int size = a.heap_size[b];
-                npop = min(size, (int)a.expansions);   // agents.py:238
+                npop = min(size, (int)nexp);   // agents.py:238
                 if (npop == 0) a.status[b] = RC_ASTAR_OPEN_EMPTY;
                 for (int i = 0; i < npop; ++i) v.popped[i] = heap_pop(v.heap_cost, v.heap_idx, size);
                 a.heap_size[b] = size;
@@ -286,8 +290,11 @@ __global__ __launch_bounds__(kBlock) void k_astar_gather_new(rc_astar_t a, const
 }
 
 // ---- push + win check + relaxation (agents.py:315-328,333-367) ------------------------------------
+// kEach: problem b's cost uses lambdas[b]; otherwise `lambda`, and `lambdas` is not read.
+template <bool kEach>
 __global__ __launch_bounds__(kBlock) void k_astar_push_relax(rc_astar_t a, const int *__restrict__ new_offset,
-                                                           const float *__restrict__ values, double lambda) {
+                                                           const float *__restrict__ values, double lambda,
+                                                           const double *__restrict__ lambdas) {
     __shared__ int s_won;
     const u32 b = blockIdx.x, tid = threadIdx.x;
     const int npop = a.n_popped[b];
@@ -309,6 +316,7 @@ __global__ __launch_bounds__(kBlock) void k_astar_push_relax(rc_astar_t a, const
     if (tid == 0) {
         int size = a.heap_size[b];
         const float *val = values + new_offset[b];
+        if (kEach) lambda = lambdas[b];
         for (int i = 0; i < cnt; ++i) {
             const int idx = first + i;
             const double cost = lambda * (double)v.G[idx] + (double)(-val[i]);   // agents.py:380-383
@@ -472,7 +480,17 @@ int rc_astar_solutions(const rc_astar_t *a, const int32_t *problems, uint32_t n,
 
 int rc_astar_pop_expand(const rc_astar_t *a, uint32_t max_states, rc_stream_t stream) {
     if (int rc = check_astar(a)) return rc;
-    hipLaunchKernelGGL(k_astar_pop_expand, dim3(a->n_problems), dim3(kBlock), 0, (hipStream_t)stream, *a, max_states);
+    hipLaunchKernelGGL(k_astar_pop_expand<false>, dim3(a->n_problems), dim3(kBlock), 0, (hipStream_t)stream, *a, max_states,
+                       (const int *)nullptr);
+    return launch_status();
+}
+
+int rc_astar_pop_expand_each(const rc_astar_t *a, uint32_t max_states, const int32_t *expansions, rc_stream_t stream) {
+    if (int rc = check_astar(a)) return rc;
+    RC_REQUIRE(expansions, RC_ERR_NULL);
+    RC_REQUIRE(((uintptr_t)expansions & 3u) == 0, RC_ERR_ALIGN);
+    hipLaunchKernelGGL(k_astar_pop_expand<true>, dim3(a->n_problems), dim3(kBlock), 0, (hipStream_t)stream, *a, max_states,
+                       (const int *)expansions);
     return launch_status();
 }
 
@@ -490,8 +508,18 @@ int rc_astar_push_relax(const rc_astar_t *a, const int32_t *new_offset, const fl
                         rc_stream_t stream) {
     if (int rc = check_astar(a)) return rc;
     RC_REQUIRE(new_offset && values, RC_ERR_NULL);
-    hipLaunchKernelGGL(k_astar_push_relax, dim3(a->n_problems), dim3(kBlock), 0, (hipStream_t)stream, *a, new_offset,
-                       values, lambda);
+    hipLaunchKernelGGL(k_astar_push_relax<false>, dim3(a->n_problems), dim3(kBlock), 0, (hipStream_t)stream, *a, new_offset,
+                       values, lambda, (const double *)nullptr);
+    return launch_status();
+}
+
+int rc_astar_push_relax_each(const rc_astar_t *a, const int32_t *new_offset, const float *values, const double *lambda,
+                             rc_stream_t stream) {
+    if (int rc = check_astar(a)) return rc;
+    RC_REQUIRE(new_offset && values && lambda, RC_ERR_NULL);
+    RC_REQUIRE(((uintptr_t)lambda & 7u) == 0, RC_ERR_ALIGN);
+    hipLaunchKernelGGL(k_astar_push_relax<true>, dim3(a->n_problems), dim3(kBlock), 0, (hipStream_t)stream, *a, new_offset,
+                       values, 0.0, lambda);
     return launch_status();
 }
 

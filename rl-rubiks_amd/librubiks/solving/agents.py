@@ -850,11 +850,16 @@ class AStar(DeepAgent):
     `search_batch` runs one such search per scramble, all on one GPU; `search` is the batch of one.
     """
 
+    sweep_parameters = ("lambda_", "expansions")   # what `search_batch` takes per game: a grid over these can be searched as one pool
+    MAX_EXPANSIONS = (2 ** 31 - 2) // 12           # 12 N + 1 node rows must be a 32-bit count
+    plant_order = "descending"                     # per-game expansions: "descending" plants the widest games first, "given" the caller's order
+
     def __init__(self, net, lambda_: float, expansions: int, net_dtype=F32_SPLIT, deterministic: bool = False):
         """deterministic: as for `MCTS` -- one layer plan of the split engine for every row count, so a problem's search does not depend
         on which other problems share its batch."""
         super().__init__(net, net_dtype, deterministic)
         self.lambda_, self.expansions = float(lambda_), int(expansions)
+        self._lambda0 = None   # game 0's lambda in the last search, where the games brought their own (`cost`)
         self.batch = None
         self._arrays = None
 
@@ -865,18 +870,19 @@ class AStar(DeepAgent):
     def __str__(self):
         return f"AStar (lambda={self.lambda_}, N={self.expansions})"
 
-    def _batch_for(self, n_problems: int, capacity: int):
-        b = self.batch
-        if b is None or b.B != n_problems or b.N != self.expansions or b.C < capacity or b.C > 4 * capacity:
+    def _batch_for(self, n_problems: int, capacity: int, expansions: int = None):
+        """expansions: the staging's row stride -- the agent's N, or the largest N of a search with per-game values."""
+        b, n_exp = self.batch, self.expansions if expansions is None else int(expansions)
+        if b is None or b.B != n_problems or b.N != n_exp or b.C < capacity or b.C > 4 * capacity:
             self.batch = None
             torch.cuda.empty_cache()
-            b = self.batch = ad.AStarBatch(n_problems, capacity, self.expansions)
+            b = self.batch = ad.AStarBatch(n_problems, capacity, n_exp)
         b.set_net(self._search_net(), self.net_dtype)   # every search: `net` may have been trained or replaced since the last one
         return b
 
     @no_grad
     def search_batch(self, states, time_limit: float = None, max_states: int = None,
-                     max_iterations: int = None, slots: int = None) -> BatchResult:
+                     max_iterations: int = None, slots: int = None, lambda_=None, expansions=None) -> BatchResult:
         """
         One A* problem per row of `states` ((G,20) int8 NumPy array or DeviceCubes).  `max_states` is the reference's per-problem
         cap (stop when len + 12 N > max_states); `time_limit` bounds the wall time of the whole search; `max_iterations` bounds
@@ -887,26 +893,83 @@ class AStar(DeepAgent):
         (rc_astar_plant).  Problems are independent, so a game's search is that of a plain batch wherever the network's values do
         not depend on the batch (deterministic=True).  Games that never got a slot before the time limit end unsolved, with 0
         nodes, status EXHAUSTED and 0 seconds.
+        lambda_, expansions: None (the agent's own value), a scalar, or an array of shape (G,) with game g's own value: game g
+        then ends exactly -- status, nodes, iterations, length, queue -- as game g of `AStar(net, lambda_[g],
+        expansions[g]).search_batch` on the same scramble, under the condition stated for `slots`.  So a grid of settings is
+        searched as one pool (the reference searches it point by point, hyper_optim.py:102-110).  lambda_ must be finite,
+        expansions an integer >= 1; `max_states` stays one number: a game with 1 + 12 expansions[g] > max_states ends EXHAUSTED
+        at its first pop, as in the reference (agents.py:236).  The batch's staging is sized for the largest expansions[g].
+        The pool plants such games -- after game 0 -- by descending expansions[g] (`plant_order`), so that the slots running at one time cost alike
+        an iteration; the result is in the caller's order.
         """
+        n_games = states.n if isinstance(states, DeviceCubes) else len(states)
+        per_game = self._per_game(n_games, lambda_, expansions)   # (raises before anything touches the device)
         time_limit, max_states = self.reset(time_limit, max_states)
-        return self._search(DeviceCubes.of(states), time_limit, max_states, max_iterations, slots)
+        roots = DeviceCubes.of(states)
+        self._lambda0 = None if per_game is None else float(per_game[0][0])
+        if per_game is None:
+            return self._search(roots, time_limit, max_states, max_iterations, slots)
+        order = np.arange(n_games)
+        if self.plant_order == "descending":   # game 0 stays first: it always gets a slot, and the inspectable attributes describe it
+            rest = order[1:]
+            order = np.concatenate([order[:1], rest[np.argsort(-per_game[1][rest], kind="stable")]])
+        if np.array_equal(order, np.arange(n_games)):
+            return self._search(roots, time_limit, max_states, max_iterations, slots, per_game)
+        pick = torch.as_tensor(order, device=roots.soa.device)
+        shuffled = DeviceCubes.empty(n_games, roots.soa.device)
+        shuffled.soa[:, :n_games] = roots.soa[:, pick]
+        got = self._search(shuffled, time_limit, max_states, max_iterations, slots, (per_game[0][order], per_game[1][order]))
+        result = BatchResult.merge(n_games, [(order, got)], got.seconds)
+        result.game_seconds = np.empty(n_games)
+        result.game_seconds[order] = got.game_seconds
+        self._explored_states = int(result.nodes[0])
+        self.action_queue = result.queues[0]
+        return result
 
-    def _search(self, roots: DeviceCubes, time_limit: float, max_states: int, max_iterations, slots) -> BatchResult:
-        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given)."""
+    def _per_game(self, n_games: int, lambda_, expansions):
+        """None if neither argument was given, else (float64 [G] lambdas, int32 [G] expansions) on the host, checked."""
+        if lambda_ is None and expansions is None:
+            return None
+        out = []
+        for name, given, own, dtype in (("lambda_", lambda_, self.lambda_, np.float64), ("expansions", expansions, self.expansions, None)):
+            arr = np.asarray(own if given is None else given)
+            if arr.dtype == object or arr.dtype.kind not in "iuf":
+                raise ValueError(f"{name}: numbers expected, got dtype {arr.dtype}")
+            if arr.ndim == 0:
+                arr = np.full(n_games, arr[()])
+            if arr.shape != (n_games,):
+                raise ValueError(f"{name}: shape {arr.shape} given, ({n_games},) expected: one value per game")
+            out.append(arr if dtype is None else arr.astype(dtype))
+        lam, n_exp = out
+        bad = np.flatnonzero(~np.isfinite(lam))
+        if len(bad):   # NaN has no place in the open list's order, and an infinite lambda times G 0 is NaN
+            raise ValueError(f"lambda_: game {int(bad[0])} has {lam[bad[0]]}; every value must be finite")
+        as_float = n_exp.astype(np.float64)
+        bad = np.flatnonzero(~np.isfinite(as_float) | (as_float != np.floor(as_float)) | (as_float < 1) | (as_float > self.MAX_EXPANSIONS))
+        if len(bad):
+            raise ValueError(f"expansions: game {int(bad[0])} has {n_exp[bad[0]]}; every value must be an integer in 1 .. {self.MAX_EXPANSIONS}")
+        return lam, n_exp.astype(np.int32)
+
+    def _search(self, roots: DeviceCubes, time_limit: float, max_states: int, max_iterations, slots, per_game=None) -> BatchResult:
+        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given).
+        per_game: (lambdas, expansions) of `_per_game` in the order of `roots`."""
         pool = SlotPool(roots.n, slots, self.tt.tock)
         S, owner = pool.S, pool.owner
         if max_iterations is not None and pool.waiting:
             raise ValueError("max_iterations applies to plain batches only (slots >= number of games)")
         cap_states = astar_time_only_capacity(S) if _unbounded(max_states) else int(max_states)
-        batch = self._batch_for(S, max(cap_states, 12 * self.expansions + 1))
+        n_max = self.expansions if per_game is None else int(per_game[1].max())
+        batch = self._batch_for(S, max(cap_states, 12 * n_max + 1), n_max)
+        each = () if per_game is None else tuple(torch.as_tensor(x, device=batch.device) for x in per_game)
         self._arrays = None
         self.tt.tick()
-        batch.reset(roots)                          # the first S scrambles; the others move in as problems finish
+        batch.reset(roots, *each)                   # the first S scrambles; the others move in as problems finish
         planted_at = np.zeros(S, dtype=np.int64)    # loop iteration at which the slot's problem was planted
         it, taken = 0, []                           # taken: (games, pinned copies, event) of extracted slots
 
         def plant(into, first):
-            batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first)
+            assert ((into >= 0) & (into < S)).all()   # (on the host: a per-slot write through a bad index would abort on the device)
+            batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first, *each)
         while max_iterations is None or it < max_iterations:
             batch.iteration(self.lambda_, cap_states)
             it += 1
@@ -928,7 +991,7 @@ class AStar(DeepAgent):
                 planted_at[pool.refill(done, plant)] = it
         torch.cuda.synchronize()
         if self._overflowed(batch.engine):   # the split engine could not represent an activation: the same search in fp32
-            return self._search(roots, time_limit, max_states, max_iterations, slots)
+            return self._search(roots, time_limit, max_states, max_iterations, slots, per_game)
         seconds = self.tt.tock()
         left = np.flatnonzero(owner >= 0)
         parts = [self._result(*t) for t in taken]
@@ -999,7 +1062,7 @@ class AStar(DeepAgent):
         from librubiks.model import make_inference_net
         eng = self.batch.engine if self.batch is not None else make_inference_net(self._search_net(), self.net_dtype)
         h = -eng.value(encode(eng, DeviceCubes.from_numpy(np.asarray(states)))).cpu().numpy().astype(np.float64)
-        return self.lambda_ * np.asarray(self.G)[indeces] + h
+        return (self.lambda_ if self._lambda0 is None else self._lambda0) * np.asarray(self.G)[indeces] + h
 
 
 # =================================================================================================

@@ -39,6 +39,8 @@ _hip.register({
     "rc_astar_pop_expand": [POINTER(_AsStruct), c_uint32, c_void_p],
     "rc_astar_gather_new": [POINTER(_AsStruct), c_void_p, c_void_p, c_size_t, c_void_p],
     "rc_astar_push_relax": [POINTER(_AsStruct), c_void_p, c_void_p, c_double, c_void_p],
+    "rc_astar_pop_expand_each": [POINTER(_AsStruct), c_uint32, c_void_p, c_void_p],
+    "rc_astar_push_relax_each": [POINTER(_AsStruct), c_void_p, c_void_p, c_void_p, c_void_p],
     "rc_astar_plant": [POINTER(_AsStruct), c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_void_p],
     "rc_astar_solutions": [POINTER(_AsStruct), c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p],
 })
@@ -48,6 +50,8 @@ NET_CHUNK = 1 << 19   # rows per network call (bounds the one-hot buffer to ~0.5
 
 class AStarBatch:
     def __init__(self, n_problems: int, capacity: int, expansions: int, device=None):
+        """expansions: N of every problem, or -- once `reset` / `plant` are given per-game values -- the largest N of any game
+        (the row stride of the per-iteration staging)."""
         self.lib = _hip.lib()
         dev = device or torch.device("cuda", torch.cuda.current_device())
         B, C, N = int(n_problems), int(capacity), int(expansions)
@@ -75,6 +79,11 @@ class AStarBatch:
         self.new_offset = z((B + 1,), torch.int32)
         self.new_states = DeviceCubes.empty(B * N * N_ACT, dev)     # compacted network input (worst case size)
         self.values = z((B * N * N_ACT,), torch.float32)
+        # per-slot settings of a batch whose games bring their own (lambda, N): written by `reset` / `plant`, read by the
+        # rc_astar_*_each entry points; `per_slot` says which pair of entry points `iteration` calls
+        self.lambda_slot = z((B,), torch.float64)
+        self.expansions_slot = zeros_or_trim((B,), torch.int32, dev, fill=N)
+        self.per_slot = False
         s = _AsStruct()
         s.n_problems, s.capacity, s.hash_size, s.expansions = B, C, self.hash_size, N
         for name, _ in _AsStruct._fields_[4:]:
@@ -98,18 +107,41 @@ class AStarBatch:
         else:
             self._oh = torch.empty((rows, getattr(self.engine, "input_width", 480)), dtype=self.engine.input_dtype, device=self.device)
 
-    def reset(self, roots: DeviceCubes):
-        """Every problem b starts from roots[b] (roots may hold more scrambles: the rest wait for `plant`)."""
+    def _check_per_game(self, lambdas, expansions, n: int):
+        assert (lambdas is None) == (expansions is None), "per-game lambda and expansions come together"
+        if lambdas is None:
+            return False
+        assert lambdas.dtype == torch.float64 and expansions.dtype == torch.int32 and lambdas.device == expansions.device == self.device
+        assert lambdas.numel() >= n and expansions.numel() >= n
+        return True
+
+    def reset(self, roots: DeviceCubes, lambdas: torch.Tensor = None, expansions: torch.Tensor = None):
+        """Every problem b starts from roots[b] (roots may hold more scrambles: the rest wait for `plant`).
+        lambdas (float64), expansions (int32, 1 .. N): device tensors with one entry per game of `roots`; slot b then runs under
+        lambdas[b], expansions[b] and `iteration` goes through the per-problem entry points.  Without them the batch runs under
+        `iteration`'s lambda and its own N, as before."""
         assert roots.n >= self.B and self.engine is not None
+        self.per_slot = self._check_per_game(lambdas, expansions, roots.n)
+        if self.per_slot:
+            self.lambda_slot.copy_(lambdas[:self.B])
+            self.expansions_slot.copy_(expansions[:self.B])
         self.hash.zero_()
         self.claim.fill_(INT_MAX)
         _hip.check(self.lib.rc_astar_init(ctypes.byref(self.struct), roots.soa.data_ptr(), roots.stride, _hip.stream_ptr()),
                    "rc_astar_init")
 
-    def plant(self, slots: torch.Tensor, roots: DeviceCubes, first: int):
+    def plant(self, slots: torch.Tensor, roots: DeviceCubes, first: int, lambdas: torch.Tensor = None, expansions: torch.Tensor = None):
         """Problem slots `slots` (int32 device tensor) restart from roots[first], roots[first + 1], ...; the others are not
-        touched, so finished problems of a running batch hand their slots to waiting scrambles between two iterations."""
+        touched, so finished problems of a running batch hand their slots to waiting scrambles between two iterations.
+        lambdas, expansions: as for `reset` (indexed by game, like `roots`); needed exactly when `reset` got them.  The planted
+        slots take their new tenants' values on the current stream, so the next pop already runs under them.  Every entry of
+        `slots` must then name a slot."""
         assert slots.dtype == torch.int32 and slots.is_cuda and slots.is_contiguous() and first + slots.numel() <= roots.n
+        assert self._check_per_game(lambdas, expansions, roots.n) == self.per_slot
+        if self.per_slot and slots.numel():
+            pick, k = slots.long(), int(slots.numel())
+            self.lambda_slot[pick] = lambdas[first:first + k]
+            self.expansions_slot[pick] = expansions[first:first + k]
         _hip.check(self.lib.rc_astar_plant(ctypes.byref(self.struct), slots.data_ptr(), int(slots.numel()), roots.soa.data_ptr(),
                                            roots.stride, int(first), _hip.stream_ptr()), "rc_astar_plant")
 
@@ -156,17 +188,25 @@ class AStarBatch:
             self.values[lo:lo + n] = self.engine.value(encode(self.engine, self.new_states, self._oh[:n], lo, n))
 
     def iteration(self, lambda_: float, max_states: int) -> int:
-        """pop N, expand, dedup, evaluate the new states, push, win check, relax.  Returns #new states."""
+        """pop N, expand, dedup, evaluate the new states, push, win check, relax.  Returns #new states.
+        A batch that was reset with per-game values runs every slot under its own (lambda, N); `lambda_` is then not used."""
         m, st = ctypes.byref(self.struct), _hip.stream_ptr()
-        _hip.check(self.lib.rc_astar_pop_expand(m, max_states, st), "rc_astar_pop_expand")
+        if self.per_slot:
+            _hip.check(self.lib.rc_astar_pop_expand_each(m, max_states, self.expansions_slot.data_ptr(), st), "rc_astar_pop_expand_each")
+        else:
+            _hip.check(self.lib.rc_astar_pop_expand(m, max_states, st), "rc_astar_pop_expand")
         torch.cumsum(self.new_count, 0, dtype=torch.int32, out=self.new_offset[1:])
         total = int(self.new_offset[-1].item())   # the one host sync per iteration: the network's row count
         if total:
             _hip.check(self.lib.rc_astar_gather_new(m, self.new_offset.data_ptr(), self.new_states.soa.data_ptr(),
                                                     self.new_states.stride, st), "rc_astar_gather_new")
             self._values_of_new(total)
-        _hip.check(self.lib.rc_astar_push_relax(m, self.new_offset.data_ptr(), self.values.data_ptr(), float(lambda_), st),
-                   "rc_astar_push_relax")
+        if self.per_slot:
+            _hip.check(self.lib.rc_astar_push_relax_each(m, self.new_offset.data_ptr(), self.values.data_ptr(), self.lambda_slot.data_ptr(), st),
+                       "rc_astar_push_relax_each")
+        else:
+            _hip.check(self.lib.rc_astar_push_relax(m, self.new_offset.data_ptr(), self.values.data_ptr(), float(lambda_), st),
+                       "rc_astar_push_relax")
         return total
 
     def any_running(self) -> bool:

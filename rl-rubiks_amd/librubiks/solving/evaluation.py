@@ -112,6 +112,49 @@ class Evaluator:
             self.log_this_depth(res[i], states[i], times[i], d)
         return res, states, times
 
+    def eval_sweep(self, agent, params: dict):
+        """
+        `agent` evaluated under P settings at once: params maps names of `agent.sweep_parameters` (AStar: lambda_, expansions) to
+        arrays of P values, point p being (params[name][p] for every name).  -> (res, states, times), each (P, D, n_games): row p
+        is what `eval` of an agent built with point p's values returns where the network's values do not depend on the batch
+        (`AStar.search_batch`).  The scrambles are those of P consecutive pooled `eval` calls -- point by point, depth by depth
+        from the global np.random stream -- and all P D n_games games are searched as one pool of `slots` slots, every game
+        under its point's values.  `max_time`, if set, bounds the whole pool at max_time x D x P.  One rank only.
+        """
+        from librubiks.cube.device import DeviceCubes
+        if _world_size() > 1:
+            raise RuntimeError("Evaluator.eval_sweep searches its pool on one GPU: the sharded search passes no per-game settings; "
+                               "run it in a single process")
+        names = list(params)
+        sweepable = getattr(agent, "sweep_parameters", ())
+        if not names or any(k not in sweepable for k in names):
+            raise ValueError(f"eval_sweep: {agent} takes per-game values for {list(sweepable)}, not for {[k for k in names if k not in sweepable]}")
+        points = [np.asarray(params[k]) for k in names]
+        P = len(points[0])
+        if P == 0 or any(v.shape != (P,) for v in points):
+            raise ValueError("eval_sweep: every parameter needs the same number (>= 1) of values, one per point")
+        D, G = len(self.scrambling_depths), self.n_games
+        pool = DeviceCubes.empty(P * D * G)
+        for p in range(P):
+            for i, d in enumerate(self.scrambling_depths):
+                depth = (lambda: np.random.randint(100, 1000)) if self._isdeep() else int(d)
+                cubes, _, _ = cube.scramble_batch(G, depth, True)
+                lo = (p * D + i) * G
+                pool.soa[:, lo:lo + G] = cubes.soa[:, :G]
+        per_game = {k: np.repeat(v, D * G) for k, v in zip(names, points)}
+        self.tt.profile(f"Evaluation of {agent}. {P} settings x {D} depths pooled")
+        out = agent.search_batch(pool, self.max_time * D * P if self.max_time else None, self.max_states, slots=self.slots, **per_game)
+        dt = self.tt.end_profile()
+        res, states = out.lengths.reshape(P, D, G).astype(np.int64), out.nodes.reshape(P, D, G).astype(np.int64)
+        each = getattr(out, "game_seconds", None)
+        times = np.asarray(each, dtype=float).reshape(P, D, G) if each is not None else np.full((P, D, G), dt / (P * D * G))
+        self.batch_seconds = [dt]
+        for p in range(P):
+            self.log("Setting " + ", ".join(f"{k}: {v[p]}" for k, v in zip(names, points)))
+            for i, d in enumerate(self.scrambling_depths):
+                self.log_this_depth(res[p, i], states[p, i], times[p, i], d)
+        return res, states, times
+
     def log_this_depth(self, res, states, times, depth, batch_seconds=None) -> dict:
         """Summary statistics of one depth (evaluation.py:96-125); logged and returned.  batch_seconds: wall time of the depth's
         batch -> `states_per_sec_batch`, the throughput of the GPU (the reference's figure, the mean of per-game states / time,
