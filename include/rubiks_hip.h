@@ -474,6 +474,26 @@ int rc_mcts_step(const rc_mcts_t *m, const float *probs, const float *values, do
                  rc_stream_t stream);
 int rc_mcts_step_head(const rc_mcts_t *m, const void *head, size_t ld, int head_is_bf16, double c, uint32_t level_budget,
                       uint32_t max_states, rc_stream_t stream);
+/* The five entry points above that take the exploration constant, with c per tree: for forests whose trees are searched under
+ * different c (a grid over c as one pool: the reference's GridSearch, librubiks/solving/hyper_optim.py:94-111, runs one agent
+ * per point).  c_each is a device array of n_trees doubles (8-byte aligned), indexed by TREE INDEX -- not by position in
+ * rc_mcts_t::active --, read once per workgroup: tree t's PUCT scores (agents.py:583-585) use c_each[t] wherever the scalar
+ * forms use c -- the float32 walk, its float64 re-evaluations and the re-validation of the previous path.
+ * What the kernel relies on: a tree's c is CONSTANT from its plant to its end.  The 16-byte walk records (best0 / best1) and
+ * the ring lines cache decisions made under it and are re-derived only for the nodes of the path being backed up; the caller
+ * writes c_each[t] (in stream order) before the plant of tree t's root and leaves it alone while the tree runs.
+ * Everything else is what the scalar forms do, launch shapes included (rc_mcts_step*_each: 256 / 512 / 1 024 threads, one or
+ * four line waves): a forest whose array holds one value evolves exactly as under the scalar export with that value.
+ * NULL m or c_each: RC_ERR_NULL; c_each not 8-byte aligned: RC_ERR_ALIGN -- both before anything is launched. */
+int rc_mcts_select_each(const rc_mcts_t *m, const double *c_each, uint32_t level_budget, rc_stream_t stream);
+int rc_mcts_backup_select_each(const rc_mcts_t *m, const float *probs, const float *values, const double *c_each,
+                               uint32_t level_budget, rc_stream_t stream);
+int rc_mcts_backup_select_head_each(const rc_mcts_t *m, const void *head, size_t ld, int head_is_bf16, const double *c_each,
+                                    uint32_t level_budget, rc_stream_t stream);
+int rc_mcts_step_each(const rc_mcts_t *m, const float *probs, const float *values, const double *c_each, uint32_t level_budget,
+                      uint32_t max_states, rc_stream_t stream);
+int rc_mcts_step_head_each(const rc_mcts_t *m, const void *head, size_t ld, int head_is_bf16, const double *c_each,
+                           uint32_t level_budget, uint32_t max_states, rc_stream_t stream);
 /* The network rows that hold a state, packed.  The tree at list position i fills the first cnt(i) of its 11 row slots: 0 if it
  * did not expand, 11 / 2 in the two root phases, else the number of its new children.  One workgroup scans the counts in list
  * order:  first[i] = sum of cnt(j < i),  *rows = R = their total,  src[first[i] + j] = 11 i + j  (first: [list length], src:

@@ -611,9 +611,13 @@ __device__ __forceinline__ u32 sel_hash(int node) { return ((u32)node * 0x9E3779
 // rc_mcts_step* gives a tree 512 / 1 024 threads there -- the parallel parts (staging, re-validation: one lane per path level)
 // of a 1 200-level descent take two rounds per thread instead of five.
 // LW: waves that check a line together (1: wave 0 alone, 64 levels per round; 4: waves 0-3, 256 levels per round -- see "line round").
-template <int MODE, bool FUSE = false, int NT = kBlock, int LW = 1>
-__global__ __launch_bounds__(NT) void k_mcts_select(rc_mcts_t m, double c, u32 level_budget, const void *__restrict__ probs_or_head,
-                                                      const float *__restrict__ values, size_t ld, bool head_bf16, u32 max_states) {
+// EACH (rc_mcts_*_each): the exploration constant comes per tree, c = c_in[tree index], one uniform load per workgroup -- a forest
+// whose trees are searched under different c (a grid over c as one pool).  A tree's c must not change between its plant and its
+// end: walk records (best0 / best1) and ring lines cache decisions made under it.  Without the flag c_in is the constant itself.
+template <int MODE, bool FUSE = false, int NT = kBlock, int LW = 1, bool EACH = false>
+__global__ __launch_bounds__(NT) void k_mcts_select(rc_mcts_t m, std::conditional_t<EACH, const double *, double> c_in, u32 level_budget,
+                                                      const void *__restrict__ probs_or_head, const float *__restrict__ values, size_t ld,
+                                                      bool head_bf16, u32 max_states) {
     __shared__ u32 s_lut[FUSE ? sizeof(kTables.lut) / 4 : 1];
     __shared__ float s_best;                // MODE > 0: the value backed up along the path
     __shared__ int s_first;                 // first level that has to be walked sequentially
@@ -637,6 +641,8 @@ __global__ __launch_bounds__(NT) void k_mcts_select(rc_mcts_t m, double c, u32 l
     const int ti = tree_of(m, slot);
     if (ti < 0) return;
     const u32 t = (u32)ti;
+    double c;
+    if constexpr (EACH) c = c_in[t]; else c = c_in;
     const bool running = m.status[t] == RC_MCTS_RUNNING;
     const bool backup = MODE > 0 && m.expanded[t];   // uniform over the workgroup
     if (!running && !backup) return;
@@ -1803,6 +1809,75 @@ int rc_mcts_step_head(const rc_mcts_t *m, const void *head, size_t ld, int head_
 #undef RC_STEP
     return launch_status();
 }
+
+// ---- the same five with c per tree (k_mcts_select<..., EACH = true>): c_each[tree index], a device array of n_trees doubles ----
+static int check_c_each(const rc_mcts_t *m, const double *c_each) {
+    RC_REQUIRE(m != nullptr && c_each != nullptr, RC_ERR_NULL);
+    RC_REQUIRE(((uintptr_t)c_each & 7u) == 0, RC_ERR_ALIGN);
+    return check_mcts(m);
+}
+
+int rc_mcts_select_each(const rc_mcts_t *m, const double *c_each, uint32_t level_budget, rc_stream_t stream) {
+    if (int rc = check_c_each(m, c_each)) return rc;
+    hipLaunchKernelGGL((k_mcts_select<0, false, kBlock, 1, true>), dim3(mcts_grid(m)), dim3(kBlock), 0, (hipStream_t)stream, *m, c_each,
+                       level_budget, (const void *)nullptr, (const float *)nullptr, (size_t)0, false, 0u);
+    return launch_status();
+}
+
+int rc_mcts_backup_select_each(const rc_mcts_t *m, const float *probs, const float *values, const double *c_each, uint32_t level_budget,
+                               rc_stream_t stream) {
+    if (int rc = check_c_each(m, c_each)) return rc;
+    RC_REQUIRE(probs && values, RC_ERR_NULL);
+    hipLaunchKernelGGL((k_mcts_select<1, false, kBlock, 1, true>), dim3(mcts_grid(m)), dim3(kBlock), 0, (hipStream_t)stream, *m, c_each,
+                       level_budget, (const void *)probs, values, (size_t)0, false, 0u);
+    return launch_status();
+}
+
+int rc_mcts_backup_select_head_each(const rc_mcts_t *m, const void *head, size_t ld, int head_is_bf16, const double *c_each,
+                                    uint32_t level_budget, rc_stream_t stream) {
+    if (int rc = check_c_each(m, c_each)) return rc;
+    RC_REQUIRE(head != nullptr, RC_ERR_NULL);
+    RC_REQUIRE(ld >= (size_t)kActions + 1, RC_ERR_RANGE);
+    hipLaunchKernelGGL((k_mcts_select<2, false, kBlock, 1, true>), dim3(mcts_grid(m)), dim3(kBlock), 0, (hipStream_t)stream, *m, c_each,
+                       level_budget, head, (const float *)nullptr, ld, head_is_bf16 != 0, 0u);
+    return launch_status();
+}
+
+// the launch shapes of rc_mcts_step / rc_mcts_step_head (step_threads, line_waves), MODE_ 1 / 2
+#define RC_STEP_EACH(MODE_, NT_, ...)                                                                                                       \
+    do {                                                                                                                                    \
+        if (line_waves(g) == 4)                                                                                                              \
+            hipLaunchKernelGGL((k_mcts_select<MODE_, true, NT_, 4, true>), dim3(g), dim3(NT_), 0, (hipStream_t)stream, *m, c_each,           \
+                               level_budget, __VA_ARGS__, max_states);                                                                      \
+        else                                                                                                                                \
+            hipLaunchKernelGGL((k_mcts_select<MODE_, true, NT_, 1, true>), dim3(g), dim3(NT_), 0, (hipStream_t)stream, *m, c_each,           \
+                               level_budget, __VA_ARGS__, max_states);                                                                      \
+    } while (0)
+
+int rc_mcts_step_each(const rc_mcts_t *m, const float *probs, const float *values, const double *c_each, uint32_t level_budget,
+                      uint32_t max_states, rc_stream_t stream) {
+    if (int rc = check_c_each(m, c_each)) return rc;
+    RC_REQUIRE(probs && values, RC_ERR_NULL);
+    RC_REQUIRE(max_states > 0, RC_ERR_RANGE);
+    const unsigned g = mcts_grid(m), nt = step_threads(g);
+    if (nt == 1024) RC_STEP_EACH(1, 1024, (const void *)probs, values, (size_t)0, false);
+    else if (nt == 512) RC_STEP_EACH(1, 512, (const void *)probs, values, (size_t)0, false);
+    else RC_STEP_EACH(1, 256, (const void *)probs, values, (size_t)0, false);
+    return launch_status();
+}
+
+int rc_mcts_step_head_each(const rc_mcts_t *m, const void *head, size_t ld, int head_is_bf16, const double *c_each, uint32_t level_budget,
+                           uint32_t max_states, rc_stream_t stream) {
+    if (int rc = check_c_each(m, c_each)) return rc;
+    RC_REQUIRE(head != nullptr, RC_ERR_NULL);
+    RC_REQUIRE(ld >= (size_t)kActions + 1 && max_states > 0, RC_ERR_RANGE);
+    const unsigned g = mcts_grid(m), nt = step_threads(g);
+    if (nt == 1024) RC_STEP_EACH(2, 1024, head, (const float *)nullptr, ld, head_is_bf16 != 0);
+    else if (nt == 512) RC_STEP_EACH(2, 512, head, (const float *)nullptr, ld, head_is_bf16 != 0);
+    else RC_STEP_EACH(2, 256, head, (const float *)nullptr, ld, head_is_bf16 != 0);
+    return launch_status();
+}
+#undef RC_STEP_EACH
 
 int rc_mcts_row_map(const rc_mcts_t *m, uint32_t *rows, int32_t *first, int32_t *src, rc_stream_t stream) {
     if (int rc = check_mcts(m)) return rc;

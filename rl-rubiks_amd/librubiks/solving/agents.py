@@ -353,6 +353,7 @@ class MCTS(DeepAgent):
     """Batched PUCT graph search with virtual loss and max-backup (reference agents.py:415-645)."""
 
     nu = 100
+    sweep_parameters = ("c",)   # what `search_batch` takes per game: a grid over these can be searched as one pool
     snapshot_trees = None      # test hook: a dict -> {game: tree_arrays()} of every tree as its search left it (before graph completion)
 
     def __init__(self, net, c: float, search_graph: bool, net_dtype=F32_SPLIT, use_graph: bool = True,
@@ -424,19 +425,50 @@ class MCTS(DeepAgent):
         return f
 
     @no_grad
-    def prepare(self, n_trees: int, max_states: int):
+    def prepare(self, n_trees: int, max_states: int, per_game_c: bool = False):
         """One-off set-up of a batched search with `n_trees` concurrent trees of capacity `max_states`, so that the search
         itself starts at full speed: allocates the forest (HBM, zero-filled), builds the inference engine and captures the HIP
         graph of every launch size the forest will be narrowed to (~0.1 s per size for the split engine: the allocations of
-        its activations).  Optional: a search on an unprepared agent does the same work on the way."""
+        its activations).  Optional: a search on an unprepared agent does the same work on the way.
+        per_game_c: the graphs of a search that brings c per game (`search_batch(c=...)`), which serve every value of c."""
         cap_states = int(max_states) if max_states and not _unbounded(max_states) else time_only_capacity(n_trees)
         forest = self._forest_for(int(n_trees), max(cap_states, 16))
         if self.use_graph:
-            forest.capture_all(self.c, cap_states)
+            forest.capture_all(md.C_PER_TREE if per_game_c else self.c, cap_states)
+
+    def sweep_refusal(self):
+        """Why `Evaluator.eval_sweep` must not pool this agent's settings, or None.  A sweep promises the rows of one `eval` per
+        setting.  The default split engine picks a layer plan by row count (see `deterministic`), and a PUCT near-tie then falls
+        differently in a pool than in a point's own batch: the engine has a form without that, so the sweep asks for it instead of
+        returning rows that the loop would not.  (The other engines have no such form: they are taken as they are.)"""
+        if self.net_dtype == F32_SPLIT:
+            return (f"{self} runs the split engine with a layer plan per row count, so a pooled game need not end as the same game "
+                    "searched point by point; build the agent with deterministic=True")
+        return None
+
+    def _per_game_c(self, n_games: int, c):
+        """None where the search runs under the agent's own c (c not given, or a scalar equal to it), else a float64 (G,) host
+        array with game g's c, checked: numbers, finite, one per game."""
+        if c is None:
+            return None
+        arr = np.asarray(c)
+        if arr.dtype == object or arr.dtype.kind not in "iuf":
+            raise ValueError(f"c: real numbers expected, got dtype {arr.dtype}")
+        if arr.ndim == 0:
+            if np.isfinite(arr) and float(arr) == self.c:
+                return None
+            arr = np.full(n_games, arr[()])
+        if arr.shape != (n_games,):
+            raise ValueError(f"c: shape {arr.shape} given, ({n_games},) expected: one value per game")
+        arr = arr.astype(np.float64)
+        bad = np.flatnonzero(~np.isfinite(arr))
+        if len(bad):   # a NaN score wins no argmax, and an infinite c times a prior of 0 is NaN
+            raise ValueError(f"c: game {int(bad[0])} has {arr[bad[0]]}; every value must be finite")
+        return arr
 
     @no_grad
     def search_batch(self, states, time_limit: float = None, max_states: int = None,
-                     max_iterations: int = None, compact: bool = True, slots: int = None) -> BatchResult:
+                     max_iterations: int = None, compact: bool = True, slots: int = None, c=None) -> BatchResult:
         """
         One MCTS tree per row of `states` ((G,20) int8 NumPy array or DeviceCubes).  `max_states` is the
         reference's per-tree cap (stop when len + 12 > max_states); `time_limit` bounds the wall time of the
@@ -448,10 +480,17 @@ class MCTS(DeepAgent):
             compact: once nobody is waiting, finished trees are dropped from the launches as the running ones become fewer
         (`MCTSForest.set_active`: a shorter list of trees, nothing moves in memory), so the stragglers continue on small
         network batches; the finished trees are turned into results where they lie, on a side stream.
+        c: None (the agent's own c), a scalar, or an array of shape (G,) with game g's own exploration constant: game g then
+        ends exactly -- status, nodes, iterations, queue, the tree itself -- as game g of `MCTS(net, c[g], ...).search_batch` on
+        the same scramble, wherever the network's outputs do not depend on the batch (deterministic=True).  So a grid over c is
+        searched as one pool (the reference searches it point by point, hyper_optim.py:102-110): every slot keeps its game's c
+        from the plant of its root on (`MCTSForest.c_slot`), and one captured graph per launch size serves every value.  Every
+        value must be a finite real number (ValueError otherwise, before anything touches the device).  None, or a scalar equal
+        to the agent's c, is the search as it always was: the scalar kernel entry points, graphs keyed by the value.
         """
         # a bounded number of iterations must end on a completed one: the three-phase form (the one-launch form of an iteration
         # expands the NEXT leaf at its end)
-        run = self.start_batch(states, time_limit, max_states, compact=compact, slots=slots, one_launch=max_iterations is None)
+        run = self.start_batch(states, time_limit, max_states, compact=compact, slots=slots, one_launch=max_iterations is None, c=c)
         assert max_iterations is None or run.S == run.n_games, "max_iterations applies to lock-step batches only"
         # a tree's first expansion (its root's) takes two lock-step iterations, every later one a single iteration
         steps = None if max_iterations is None else max_iterations + 1
@@ -463,9 +502,11 @@ class MCTS(DeepAgent):
 
     @no_grad
     def start_batch(self, states, time_limit: float = None, max_states: int = None, compact: bool = True,
-                    slots: int = None, one_launch: bool = True) -> "MCTSRun":
+                    slots: int = None, one_launch: bool = True, c=None) -> "MCTSRun":
+        """c: as for `search_batch`."""
+        per_game_c = self._per_game_c(states.n if isinstance(states, DeviceCubes) else len(states), c)   # (raises before anything touches the device)
         time_limit, max_states = self.reset(time_limit, max_states)
-        return MCTSRun(self, DeviceCubes.of(states), time_limit, max_states, compact, slots, one_launch)
+        return MCTSRun(self, DeviceCubes.of(states), time_limit, max_states, compact, slots, one_launch, per_game_c)
 
     # ---- the reference's single-state API ----------------------------------------------------------
     def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
@@ -562,10 +603,15 @@ class MCTSRun(SlotPool):
     175 000, the reference's default max_states, took 0.55 s per halving).
     """
 
-    def __init__(self, agent: "MCTS", roots: DeviceCubes, time_limit: float, max_states: int, compact: bool, slots, one_launch: bool = True):
+    def __init__(self, agent: "MCTS", roots: DeviceCubes, time_limit: float, max_states: int, compact: bool, slots, one_launch: bool = True,
+                 c_games: np.ndarray = None):
+        """c_games: None -- every tree under `agent.c` --, or game g's own c (float64 [G], checked: `MCTS._per_game_c`): every plant
+        hands its slots their games' values and the iterations go through the per-tree entry points (`md.C_PER_TREE`)."""
         super().__init__(roots.n, slots, agent.tt.tock)
         self.agent, self.roots, self.time_limit, self.compact = agent, roots, time_limit, compact
         self.max_states, self.slots, self.one_launch = max_states, slots, one_launch
+        self.c_games = c_games
+        self.c = agent.c if c_games is None else md.C_PER_TREE     # what `steps` / `step` / `close_pending` get
         S = self.S
         self.cap_states = time_only_capacity(S) if _unbounded(max_states) else int(max_states)
         forest = self.forest = agent._forest_for(S, max(self.cap_states, 16))
@@ -573,7 +619,8 @@ class MCTSRun(SlotPool):
         agent.tt.tick()
         forest.set_active(None)
         self.plant_states = self.cap_states if one_launch else None   # one-launch iterations: roots expanded by the plant itself
-        forest.plant(None, roots, 0, self.plant_states)       # the first S scrambles; the others move in as trees finish
+        self.c_dev = None if c_games is None else _to_device_async(c_games, forest.device)
+        forest.plant(None, roots, 0, self.plant_states, c=self.c_dev)   # the first S scrambles; the others move in as trees finish
         # iterations that may be queued before the host has looked at the node counts: what a planted tree's first rows cover
         # (16 384 rows: its first ~1 360 iterations), so that a long `sync_every` cannot make trees sit out behind the kernel's guard
         forest._steps_covered = min(2 * agent.sync_every, max(1, (forest._first_rows() - 14) // 12))
@@ -695,7 +742,7 @@ class MCTSRun(SlotPool):
         if max_steps is not None:
             n_steps = min(n_steps, max_steps)
         t0 = perf_counter()
-        forest.steps(n_steps, agent.c, self.cap_states, agent.use_graph)
+        forest.steps(n_steps, self.c, self.cap_states, agent.use_graph)
         self.it += n_steps
         self.stats["iterations"] = self.it
         self.snapshots.append((self.q, forest, *forest.status_snapshot(), self.it))
@@ -760,7 +807,7 @@ class MCTSRun(SlotPool):
             self._harvest(done)
             def plant(slots, first):   # the waiting scrambles move in: roots evaluated by the next two iterations
                 idx = _to_device_async(slots.astype(np.int32), forest.status.device)
-                forest.plant(idx, self.roots, first, self.plant_states, slots_host=slots)
+                forest.plant(idx, self.roots, first, self.plant_states, slots_host=slots, c=self.c_dev)
             self.stale_until[self.refill(done, plant)] = self.q - 1     # every snapshot queued so far predates the adoption
             self.stats["refills"] += 1
         elif not waiting and self.compact and forest.rung_for(n_run) < forest.G:
@@ -791,7 +838,7 @@ class MCTSRun(SlotPool):
             forest.grow_paths(forest.path_len.cpu().numpy())
             forest._steps_covered = 2
             forest.set_active(lag)
-            forest.step(self.agent.c, self.cap_states, self.agent.use_graph)
+            forest.step(self.c, self.cap_states, self.agent.use_graph)
             self.it += 1
             stepped = True
         if stepped:
@@ -813,7 +860,7 @@ class MCTSRun(SlotPool):
         if self.one_launch and bool(forest.expanded.any().item()):
             # the search stopped on time or on a step count (or its last step solved a tree): the expansions that step left
             # pending are backed up and followed by their descent, as the reference's loop would have done (agents.py:476-490)
-            forest.close_pending(agent.c)
+            forest.close_pending(self.c)
         torch.cuda.synchronize()
         seconds = agent.tt.tock()
         forest.grow(forest.n_nodes.cpu().numpy(), 0)     # the final node counts (what result extraction reads of a tree)
@@ -833,7 +880,7 @@ class MCTSRun(SlotPool):
         self.close(result, seconds, md.EXHAUSTED)
         self.done = True
         if agent._overflowed(forest.engine):   # the split engine could not represent an activation: the same search in fp32
-            again = MCTSRun(agent, self.roots, self.time_limit, self.max_states, self.compact, self.slots, self.one_launch)
+            again = MCTSRun(agent, self.roots, self.time_limit, self.max_states, self.compact, self.slots, self.one_launch, self.c_games)
             while not again.done:
                 again.round()
             return again.finish()

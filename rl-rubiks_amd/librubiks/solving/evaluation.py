@@ -114,12 +114,14 @@ class Evaluator:
 
     def eval_sweep(self, agent, params: dict):
         """
-        `agent` evaluated under P settings at once: params maps names of `agent.sweep_parameters` (AStar: lambda_, expansions) to
-        arrays of P values, point p being (params[name][p] for every name).  -> (res, states, times), each (P, D, n_games): row p
-        is what `eval` of an agent built with point p's values returns where the network's values do not depend on the batch
-        (`AStar.search_batch`).  The scrambles are those of P consecutive pooled `eval` calls -- point by point, depth by depth
-        from the global np.random stream -- and all P D n_games games are searched as one pool of `slots` slots, every game
-        under its point's values.  `max_time`, if set, bounds the whole pool at max_time x D x P.  One rank only.
+        `agent` evaluated under P settings at once: params maps names of `agent.sweep_parameters` (AStar: lambda_, expansions;
+        MCTS: c) to arrays of P values, point p being (params[name][p] for every name).  -> (res, states, times), each
+        (P, D, n_games): row p is what `eval` of an agent built with point p's values returns where the network's values do not
+        depend on the batch (`AStar.search_batch`, `MCTS.search_batch`).  The scrambles are those of P consecutive pooled `eval`
+        calls -- point by point, depth by depth from the global np.random stream -- and all P D n_games games are searched as
+        one pool of `slots` slots, every game under its point's values.  `max_time`, if set, bounds the whole pool at
+        max_time x D x P.  One rank only.  An agent that knows its rows would not be those of `eval` says so (`sweep_refusal`: MCTS on
+        the default split engine, whose layer plan depends on the row count, asks for deterministic=True): ValueError.
         """
         from librubiks.cube.device import DeviceCubes
         if _world_size() > 1:
@@ -129,6 +131,9 @@ class Evaluator:
         sweepable = getattr(agent, "sweep_parameters", ())
         if not names or any(k not in sweepable for k in names):
             raise ValueError(f"eval_sweep: {agent} takes per-game values for {list(sweepable)}, not for {[k for k in names if k not in sweepable]}")
+        refusal = getattr(agent, "sweep_refusal", lambda: None)()   # (an agent may know that its rows would not be those of `eval`)
+        if refusal:
+            raise ValueError(f"eval_sweep: {refusal}")
         points = [np.asarray(params[k]) for k in names]
         P = len(points[0])
         if P == 0 or any(v.shape != (P,) for v in points):

@@ -8,7 +8,7 @@ class names, constructor and method signatures, the four result attributes), wri
 
 The reference walks a grid point by point, with a new agent and one `Evaluator.eval` each.  A point is ~100 games -- a small batch for
 a 256-CU device -- and every point sets up and drops a batch of its own.  Where the agent's `search_batch` takes the grid's
-parameters per game (`agent_class.sweep_parameters`; AStar: lambda_, expansions), the whole grid is ONE continuous-batching pool
+parameters per game (`agent_class.sweep_parameters`; AStar: lambda_, expansions; MCTS: c), the whole grid is ONE continuous-batching pool
 (`Evaluator.eval_sweep`): `GridSearch(..., pooled=True)`.  Both routes draw the same scrambles from the global np.random stream and,
 with deterministic agents under a `max_states` bound, end with the same histories.
 
@@ -22,6 +22,9 @@ from librubiks.utils import NullLogger
 
 # `GridSearch(pooled=None)` where the pooled route applies: the measured choice (profiles/astar_sweep_probe.txt).
 POOLED_BY_DEFAULT = True
+# ... and per agent class (its name, or that of a base class), each from that class's own measurement: AStar as above (loop 140-148 s,
+# pool 33 s); MCTS profiles/mcts_grid_probe.txt (the reference's 125-point grid over c: loop 108 s, pool 31 s).
+POOLED_BY_DEFAULT_FOR = {"AStar": True, "MCTS": True}
 # Exploration constants of the acquisition function handed to bayes_opt: the reference's values (hyper_optim.py:161).
 ACQUISITION_KAPPA, ACQUISITION_XI = 2.5, 0.2
 
@@ -102,7 +105,8 @@ class GridSearch(Optimizer):
     Every point of a regular grid (`grid_points`).  pooled: False -- the reference's loop, `target_function` point by point;
     True -- after `objective_from_evaluator`, the whole grid in one `evaluator.eval_sweep` (the agent class must take every grid
     parameter per game); None -- the pool where it applies (`pooled_route_applies`) and has been measured faster
-    (`POOLED_BY_DEFAULT`), else the loop.
+    for the agent class (`POOLED_BY_DEFAULT`, `POOLED_BY_DEFAULT_FOR`) and the agent does not refuse it (`sweep_refusal`), else the
+    loop.
     """
 
     def __init__(self, target_function, parameters: dict, logger=NullLogger(), pooled: bool = None):
@@ -120,16 +124,26 @@ class GridSearch(Optimizer):
         sweepable = getattr(self.agent_class, "sweep_parameters", ())
         return all(kw in sweepable for kw in self.parameters) and bool(ev.max_states) and bool(getattr(ev, "slots", None)) and _world_size() == 1
 
+    def pooled_by_default(self) -> bool:
+        """The measured choice for the agent class (`POOLED_BY_DEFAULT_FOR`), else `POOLED_BY_DEFAULT`."""
+        for cls in getattr(self.agent_class, "__mro__", ()):
+            if cls.__name__ in POOLED_BY_DEFAULT_FOR:
+                return POOLED_BY_DEFAULT_FOR[cls.__name__]
+        return POOLED_BY_DEFAULT
+
     def optimize(self, iterations: int):
         points = grid_points(self.parameters, iterations)
-        pooled = (POOLED_BY_DEFAULT and self.pooled_route_applies()) if self.pooled is None else bool(self.pooled)
+        pooled = (self.pooled_by_default() and self.pooled_route_applies()) if self.pooled is None else bool(self.pooled)
         if pooled and self.evaluator is None:
             raise ValueError("GridSearch(pooled=True) evaluates the grid through an Evaluator: call objective_from_evaluator first")
+        agent = self._agent_for(points[0]) if pooled else None
+        if pooled and self.pooled is None and getattr(agent, "sweep_refusal", lambda: None)():
+            pooled = False     # the automatic choice takes no pool that `eval_sweep` would refuse (MCTS on a batch-dependent engine)
         self.logger.section(f"{self}: {len(points)} settings, " + ("searched as one pool" if pooled else "one after the other"))
         if pooled:
             prepared = [self.param_prepper(dict(p)) for p in points]   # (as the loop prepares each setting before it builds the agent)
             per_setting = {kw: np.array([p[kw] for p in prepared]) for kw in self.parameters}
-            res, states, times = self.evaluator.eval_sweep(self._agent_for(points[0]), per_setting)
+            res, states, times = self.evaluator.eval_sweep(agent, per_setting)
             scores = [self._scored(res[i], states[i], times[i])[0] for i in range(len(points))]
             for step, (setting, score) in enumerate(zip(points, scores)):
                 self._keep(step, setting, score)

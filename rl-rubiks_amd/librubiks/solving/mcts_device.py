@@ -56,6 +56,12 @@ _hip.register({
     "rc_mcts_plant_expanded": [POINTER(_McStruct), c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_uint32, c_void_p],
     "rc_mcts_step": [POINTER(_McStruct), c_void_p, c_void_p, c_double, c_uint32, c_uint32, c_void_p],
     "rc_mcts_step_head": [POINTER(_McStruct), c_void_p, c_size_t, c_int, c_double, c_uint32, c_uint32, c_void_p],
+    # c per tree: a device array of n_trees doubles where the five above take the constant
+    "rc_mcts_select_each": [POINTER(_McStruct), c_void_p, c_uint32, c_void_p],
+    "rc_mcts_backup_select_each": [POINTER(_McStruct), c_void_p, c_void_p, c_void_p, c_uint32, c_void_p],
+    "rc_mcts_backup_select_head_each": [POINTER(_McStruct), c_void_p, c_size_t, c_int, c_void_p, c_uint32, c_void_p],
+    "rc_mcts_step_each": [POINTER(_McStruct), c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p],
+    "rc_mcts_step_head_each": [POINTER(_McStruct), c_void_p, c_size_t, c_int, c_void_p, c_uint32, c_uint32, c_void_p],
     "rc_mcts_row_map": [POINTER(_McStruct), c_void_p, c_void_p, c_void_p, c_void_p],
     "rc_mcts_complete_graph": [POINTER(_McStruct), c_void_p],
     "rc_mcts_shorten": [POINTER(_McStruct), c_void_p],
@@ -97,6 +103,18 @@ _NODE_FIELDS = {"N": (0, 12, torch.int32), "W": (12, 24, torch.float32), "rec": 
 
 
 MAX_CAPACITY = (1 << 24) - 2   # nodes per tree: capacity + 1 rows of 256 bytes, addressed by 32-bit byte offsets (rc_mcts_t, tree_bufs)
+
+
+class _PerTreeC:
+    """What `step` / `steps` / `close_pending` / `capture_all` take in place of a float c: every tree runs under its own entry of
+    `MCTSForest.c_slot` (the rc_mcts_*_each entry points).  A captured graph then names the array, not a value: one graph per
+    launch size serves every c."""
+
+    def __repr__(self):
+        return "C_PER_TREE"
+
+
+C_PER_TREE = _PerTreeC()
 
 RUNG_RATIO = 0.95   # measured on configs[1] to completion, same box: 0.8 1.772 s, 0.9 1.735, 0.93 1.715, 0.95 1.710, 0.97 1.703 (profiles/r3_rung_ratio_ab.txt)
 
@@ -301,6 +319,9 @@ class MCTSForest:
         self.row_count = z((4,), torch.int32)
         self.row_first = z((B,), torch.int32)
         self.row_src = z((ROWS * B,), torch.int32)
+        # the exploration constant of the tree in every slot, for forests stepped with C_PER_TREE: written by `plant`, read by the
+        # rc_mcts_*_each entry points (by tree index); static, like every buffer a captured graph names
+        self.c_slot = z((B,), torch.float64)
         self.probs = z((ROWS * B, N_ACT), torch.float32)     # static network outputs (graph capture)
         self.values = z((ROWS * B,), torch.float32)
         s = _McStruct()
@@ -334,7 +355,7 @@ class MCTSForest:
         self.engine = None
         self._net_fp = None
         self._oh = None
-        self._graphs = {}          # (G, c, max_states, level budget, form) -> captured iteration
+        self._graphs = {}          # (G, c or C_PER_TREE, max_states, level budget, form) -> captured iteration
         self._packs = {}           # G -> whether the engine takes packed rows at that launch size (`_packing`)
         self._graph_pool = None    # one memory pool for all of them: they never run concurrently
 
@@ -709,10 +730,14 @@ class MCTSForest:
     fused_step = True   # iterations as [network -> rc_mcts_step*] (expansion at the END of a step) when the trees were planted for it
     _one_launch = False
 
-    def plant(self, slots, roots: DeviceCubes, first: int = 0, max_states: int = None, slots_host: np.ndarray = None):
+    def plant(self, slots, roots: DeviceCubes, first: int = 0, max_states: int = None, slots_host: np.ndarray = None,
+              c: torch.Tensor = None):
         """Trees `slots` (int32 device tensor, or None for all) restart from roots[first], roots[first + 1], ...: their
         hash tables are cleared by the kernel, nothing else needs clearing (a node's rows are initialised when it is
         created).  Safe between two iterations of a running forest: other trees are not touched.
+        c (float64 device tensor, indexed by game like `roots`): the planted slots take c[first], c[first + 1], ... into `c_slot`
+        on the current stream, ahead of the plant kernel, so a tree stepped with C_PER_TREE runs under its game's c from its
+        first descent to its end.  Every entry of `slots` must then name a slot.
         max_states (the search's per-tree cap): the roots are expanded right here (rc_mcts_plant_expanded) and the forest's
         iterations become [network -> one tree kernel that backs up, descends and expands the next leaf]; without it the
         three-phase form [expand -> network -> backup + descent] is used.  Planting all trees chooses the form, planting some
@@ -728,6 +753,12 @@ class MCTSForest:
         if slots is None:
             self._one_launch = one
         assert one == self._one_launch, "trees planted into a running forest must use the form its iterations run in"
+        if c is not None and n:
+            assert c.dtype == torch.float64 and c.device == self.c_slot.device and c.numel() >= first + n
+            if slots is None:
+                self.c_slot.copy_(c[first:first + n])
+            else:
+                self.c_slot[slots.long()] = c[first:first + n]
         if one:
             assert self.G == self.B, "roots are expanded into the rows of list position == tree index: plant before narrowing"
             _hip.check(self.lib.rc_mcts_plant_expanded(ctypes.byref(self.struct), None if slots is None else slots.data_ptr(), n,
@@ -760,10 +791,18 @@ class MCTSForest:
                                             self.row_src.data_ptr(), _hip.stream_ptr()), "rc_mcts_row_map")
         return self.row_count, self.row_first, self.row_src
 
-    def _graph_key(self, c: float, max_states: int):
-        return (self.G, float(c), int(max_states), int(self.level_budget), (self._one_launch, self._packing()))   # the form of the iteration
+    def _graph_key(self, c, max_states: int):
+        """c: a float, or C_PER_TREE -- the graph then reads `c_slot` at replay and serves every value."""
+        return (self.G, c if c is C_PER_TREE else float(c), int(max_states), int(self.level_budget),
+                (self._one_launch, self._packing()))   # the form of the iteration
 
-    def _iteration(self, c: float, max_states: int):
+    def _c_call(self, name: str, c):
+        """(entry point, its c argument, its name): `name` with a float c, `name`_each with `c_slot` for C_PER_TREE."""
+        if c is C_PER_TREE:
+            return getattr(self.lib, name + "_each"), self.c_slot.data_ptr(), name + "_each"
+        return getattr(self.lib, name), c, name
+
+    def _iteration(self, c, max_states: int):
         st = _hip.stream_ptr()
         m = ctypes.byref(self.struct)
         if self._one_launch:   # the rows were left by the previous step's expansion (or by the plant): network, then ONE tree kernel
@@ -776,25 +815,25 @@ class MCTSForest:
                     head = self.engine.head_cubes(cubes, None if self._x1 is None else self._x1[:rows], self.row_count, self.row_src)
                 else:
                     head = self.engine.head_cubes(cubes, None if self._x1 is None else self._x1[:rows])
-                _hip.check(self.lib.rc_mcts_step_head(m, head.data_ptr(), head.stride(0), int(head.dtype == torch.bfloat16), c,
-                                                      self.level_budget, max_states, st), "rc_mcts_step_head")
+                fn, c_arg, name = self._c_call("rc_mcts_step_head", c)
+                _hip.check(fn(m, head.data_ptr(), head.stride(0), int(head.dtype == torch.bfloat16), c_arg, self.level_budget, max_states, st), name)
             else:
                 self._evaluate_children()
-                _hip.check(self.lib.rc_mcts_step(m, self.probs.data_ptr(), self.values.data_ptr(), c, self.level_budget, max_states, st),
-                           "rc_mcts_step")
+                fn, c_arg, name = self._c_call("rc_mcts_step", c)
+                _hip.check(fn(m, self.probs.data_ptr(), self.values.data_ptr(), c_arg, self.level_budget, max_states, st), name)
             return
         _hip.check(self.lib.rc_mcts_expand(m, max_states, st), "rc_mcts_expand")
         if self._fused:   # head GEMM output (12 logits + value per row) goes straight into the backup kernel
             cubes, rows = self._net_input()
             head = self.engine.head_cubes(cubes, None if self._x1 is None else self._x1[:rows])
-            _hip.check(self.lib.rc_mcts_backup_select_head(m, head.data_ptr(), head.stride(0), int(head.dtype == torch.bfloat16),
-                                                           c, self.level_budget, st), "rc_mcts_backup_select_head")
+            fn, c_arg, name = self._c_call("rc_mcts_backup_select_head", c)
+            _hip.check(fn(m, head.data_ptr(), head.stride(0), int(head.dtype == torch.bfloat16), c_arg, self.level_budget, st), name)
         else:
             self._evaluate_children()
-            _hip.check(self.lib.rc_mcts_backup_select(m, self.probs.data_ptr(), self.values.data_ptr(), c, self.level_budget, st),
-                       "rc_mcts_backup_select")
+            fn, c_arg, name = self._c_call("rc_mcts_backup_select", c)
+            _hip.check(fn(m, self.probs.data_ptr(), self.values.data_ptr(), c_arg, self.level_budget, st), name)
 
-    def close_pending(self, c: float):
+    def close_pending(self, c):
         """One-launch iterations end with the NEXT leaf's expansion, so a search that stops while trees are running (time limit,
         step count) -- or right after the step whose expansion solved a tree -- leaves expansions that were never backed up.
         This is the second half of the three-phase iteration for them: network on the rows the last step left, backup, and the
@@ -806,15 +845,17 @@ class MCTSForest:
         if self._fused:
             cubes, rows = self._net_input()
             head = self.engine.head_cubes(cubes, None if self._x1 is None else self._x1[:rows])
-            _hip.check(self.lib.rc_mcts_backup_select_head(m, head.data_ptr(), head.stride(0), int(head.dtype == torch.bfloat16),
-                                                           c, 0, st), "rc_mcts_backup_select_head")
+            fn, c_arg, name = self._c_call("rc_mcts_backup_select_head", c)
+            _hip.check(fn(m, head.data_ptr(), head.stride(0), int(head.dtype == torch.bfloat16), c_arg, 0, st), name)
         else:
             self._evaluate_children()
-            _hip.check(self.lib.rc_mcts_backup_select(m, self.probs.data_ptr(), self.values.data_ptr(), c, 0, st), "rc_mcts_backup_select")
+            fn, c_arg, name = self._c_call("rc_mcts_backup_select", c)
+            _hip.check(fn(m, self.probs.data_ptr(), self.values.data_ptr(), c_arg, 0, st), name)
         self.expanded.zero_()
 
-    def step(self, c: float, max_states: int, use_graph: bool = True):
+    def step(self, c, max_states: int, use_graph: bool = True):
         """One lock-step iteration of every running tree: expand -> network -> backup + select (one kernel).
+        c: the exploration constant of every tree, or C_PER_TREE: tree t runs under `c_slot[t]`, as `plant` wrote it.
         A freshly planted tree spends its first two steps on its root (evaluation + expansion, then backup + first descent)."""
         assert not self.results_only
         if self.vmm or self.path_vmm:
@@ -842,7 +883,7 @@ class MCTSForest:
 
     GRAPH_STEPS = max(1, int(os.environ.get("RUBIKS_GRAPH_STEPS", "4")))   # iterations per replayed graph in `steps` (1: one graph launch per iteration)
 
-    def _graph_of_steps(self, c: float, max_states: int):
+    def _graph_of_steps(self, c, max_states: int):
         """The HIP graph of GRAPH_STEPS consecutive iterations at the current launch size (captured on first use, once the
         one-iteration graph of that size exists: its eager run has settled the library's kernel choices and the allocator)."""
         key = self._graph_key(c, max_states)
@@ -858,7 +899,7 @@ class MCTSForest:
             self._graphs[key + (self.GRAPH_STEPS,)] = g
         return g
 
-    def steps(self, n: int, c: float, max_states: int, use_graph: bool = True):
+    def steps(self, n: int, c, max_states: int, use_graph: bool = True):
         """n lock-step iterations.  Between two graph launches the queue idles ~9 us (the kernels inside a graph follow each other
         without a gap: profiles/r6_step_timelines_f32s.txt), 5 % of a 32-tree step -- so the iterations go out GRAPH_STEPS to a graph
         launch, the remainder one by one.  The host looks at the trees between calls, never between the iterations of a call."""
@@ -876,7 +917,7 @@ class MCTSForest:
             g.replay()
             n -= U
 
-    def capture_all(self, c: float, max_states: int):
+    def capture_all(self, c, max_states: int):
         """Captures the iteration's HIP graph for every launch size of the ladder (`rungs`) ahead of time, on an idle forest (every
         tree marked finished: the tree kernels return at once, the network runs on whatever the row buffers hold).  One-off set-up
         per forest and (c, max_states): a search started afterwards replays graphs from its first iteration on, however it narrows."""
