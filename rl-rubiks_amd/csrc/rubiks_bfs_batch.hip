@@ -90,7 +90,8 @@ __global__ __launch_bounds__(kBlock) void k_bfsb_plant(rc_bfs_batch_t b, const i
     next_chunk(b, s, 1, 0, 1);
 }
 
-// what a row thread needs of its slot; n_par is 0 for a slot that does nothing
+// what a row thread needs of its slot; n_par is 0 for a slot that does nothing, which is every slot that is not running: the
+// other words of a slot that was never planted are whatever the memory held
 struct SlotRow {
     u32 s, local, n_par;
     size_t row0;
@@ -102,7 +103,7 @@ __device__ __forceinline__ SlotRow slot_row(const rc_bfs_batch_t &b, u32 r, int 
     q.s = r / seg;
     q.local = r - q.s * seg;
     q.row0 = (size_t)q.s * seg;
-    q.n_par = (u32)word(b, n_word, q.s);
+    q.n_par = word(b, RC_BFSB_W_STATUS, q.s) == RC_BFSB_RUNNING ? (u32)word(b, n_word, q.s) : 0;
     return q;
 }
 
