@@ -908,6 +908,87 @@ int rc_bfs_batch_plant(const rc_bfs_batch_t *b, const int32_t *slots, uint32_t n
  * the slots that have just solved (agents.py:112-115), root first, into their queue rows.  Finished and empty slots do nothing. */
 int rc_bfs_batch_step(const rc_bfs_batch_t *b, rc_stream_t stream);
 
+/* ---- shortening action queues through the graph of the states they visit (csrc/rubiks_shorten.hip) -------------------
+ *
+ * The reference shortens the solution of a solved MCTS(search_graph=True) only: _complete_graph (agents.py:597-611) fills the
+ * neighbour table of the tree, _shorten_action_queue (agents.py:613-633) runs an ordered breadth-first search from the root to
+ * the solved node.  Here the same two procedures run on the graph of a QUEUE, whichever agent made it.  For game g with root
+ * s_0 and queue a_0 .. a_{L-1}, s_{i+1} = s_i turned by a_i.  The nodes are the distinct states among s_0 .. s_L: node 1 + p is
+ * the state whose first occurrence is at position p (so node 1 is the root and the ids of a game lie in 1 .. L + 1, with gaps
+ * where a state returns); 0 is "no node".  nbr[v][a] is the node of state(v) turned by a, or 0 (_complete_graph with every node
+ * a leaf).  The target is the node of s_L.  The result is the empty queue if the target is node 1 (agents.py:614), else what the
+ * FIFO search of agents.py:616-633 returns: neighbours scanned in action order 0 .. 11, visited nodes skipped, the first scan
+ * that meets the target ends the search, actions read back along the discoverers.  It is a shortest route within that graph,
+ * never longer than L, ends in s_L, and depends on the game alone.
+ *
+ * Workspace: game g owns positions pos_off[g] .. pos_off[g + 1] - 1 (at least L + 1 of them) of the per-position arrays and
+ * cells hash_off[g] .. hash_off[g + 1] - 1 of `hash`, a power of two >= 2 (L + 1).  Rows of the per-node arrays (nbr, claim) are
+ * indexed by position too: node v of game g is row pos_off[g] + v - 1.  All pointers are device pointers.
+ * rc_shorten_workspace_bytes(P, H) = r(16 P) + r(4 P) + r(48 P) + r(8 P) + 2 r(4 P) + r(4 H) with r(x) = x rounded up to 256:
+ * keys, ids, nbr, claim, the two frontiers and the hash cells, 84 bytes per position and 4 per cell (8 .. 16 more per position).
+ *
+ * Lengths: parent << 4 | action and the scan index 12 i + a are int32 words, so L + 1 < 2^27: L <= RC_SHORTEN_MAX_LEN.  The host
+ * states the longest selected queue in max_len; an entry point returns RC_ERR_RANGE if that exceeds RC_SHORTEN_MAX_LEN or the
+ * queue rows, and a game whose lens[g] or offsets do not fit what the struct states ends RC_SHORTEN_FAILED untouched. */
+#define RC_SHORTEN_MAX_LEN ((1 << 27) - 2)
+#define RC_SHORTEN_OK 0          /* so far every step has run; after rc_shorten_bfs: out_lens[g] holds the result's length */
+#define RC_SHORTEN_SKIPPED 1     /* select[g] == 0: the game is left alone */
+#define RC_SHORTEN_BAD_ACTION 2  /* a queue byte >= 12 inside the game's length: found before it indexes anything */
+#define RC_SHORTEN_FAILED 3      /* a length, an offset, a table word or an index read from memory does not name this game's data */
+#define RC_SHORTEN_NO_ROOM 4     /* the result is longer than out_width: out_lens[g] holds its length, no byte of the row is written */
+
+typedef struct rc_shorten {
+    uint32_t n_games;         /* G >= 1 */
+    uint32_t queue_width;     /* bytes per row of `queues` */
+    uint32_t out_width;       /* bytes per row of `out_queues` */
+    uint32_t max_len;         /* the host's word: no selected game has lens[g] above it; <= min(queue_width, RC_SHORTEN_MAX_LEN) */
+    size_t stride;            /* bytes between the planes of roots_soa: multiple of 16, >= round_up(G, 16) */
+    size_t total_positions;   /* P = pos_off[G]: rows of the per-position arrays */
+    size_t total_hash_cells;  /* H = hash_off[G] */
+    const int8_t *roots_soa;  /* [20][stride] root state of game g in column g */
+    const uint8_t *queues;    /* [G][queue_width] */
+    const int32_t *lens;      /* [G] L */
+    const uint8_t *select;    /* [G] 0: leave the game alone */
+    const uint64_t *pos_off;  /* [G + 1] prefix sums made on the host: >= L + 1 positions per selected game */
+    const uint64_t *hash_off; /* [G + 1] ... and a power of two >= 2 (L + 1) of cells */
+    uint32_t *keys;           /* [P][4] the packed state of every position (20 codes of 5 bits, 6 per word), 16-byte aligned */
+    int32_t *ids;             /* [P] node of the position: 1 + the first position of its state */
+    int32_t *nbr;             /* [P][12] row v - 1: the neighbours of node v; rows of positions that are no first occurrence are not written */
+    int32_t *claim;           /* [P][2] row v - 1: {smallest scan index that reached v (INT_MAX: none), parent << 4 | action (0: not
+                                 visited, -1: the root)} */
+    int32_t *frontier_a;      /* [P] the two frontiers of the search, swapped level by level */
+    int32_t *frontier_b;      /* [P] */
+    int32_t *hash;            /* [H] open addressing, linear probing: a cell holds the node of a state, 0 = free; 16-byte aligned */
+    uint8_t *out_queues;      /* [G][out_width] the result, root first */
+    int32_t *out_lens;        /* [G] its length; -1 where there is none (skipped, bad action, failed) */
+    int32_t *status;          /* [G] RC_SHORTEN_* */
+} rc_shorten_t;
+
+size_t rc_shorten_struct_bytes(void);
+/* Host only: bytes of the workspace arrays of P positions and H hash cells by the formula above (each array starts on a 256-byte
+ * boundary); 0 if the sum does not fit size_t. */
+size_t rc_shorten_workspace_bytes(size_t total_positions, size_t total_hash_cells);
+/* The states of agents.py:597-611's `self.states` / `self.indices` for every selected game: status and out_lens are written for
+ * ALL games (SKIPPED / BAD_ACTION / FAILED / OK; -1); then for the games that are OK the queue is replayed from the root (20
+ * lanes per game, one cubie each), keys[p] is stored for p = 0 .. L, the hash cells are cleared, every position is inserted with
+ * full-key compare -- equal states elect their smallest position, exactly, whatever the order of the inserts -- and ids[p] =
+ * the elected node.  Three launches and one memset. */
+int rc_shorten_index(const rc_shorten_t *s, rc_stream_t stream);
+/* _complete_graph (agents.py:597-611) with every node a leaf: nbr[v][a] for every node v (position p with ids[p] == p + 1) and
+ * a = 0 .. 11 by one table probe each, bounded by the table's size.  A cell that does not name a node of the game (outside
+ * 1 .. L + 1, or a position that is not its own node) ends the game RC_SHORTEN_FAILED.  Games that are not OK are not touched. */
+int rc_shorten_neighbours(const rc_shorten_t *s, rc_stream_t stream);
+/* _shorten_action_queue (agents.py:613-633) for every game that is OK, one workgroup each: target = ids[L]; target 1 gives
+ * out_lens[g] = 0 (agents.py:614).  Else level-synchronous: every unvisited neighbour of the frontier is claimed by the smallest
+ * scan index 12 i + a that reaches it (i: place in the frontier), the winners enter the next frontier in scan-index order, which
+ * is the order of the reference's FIFO; the level that claims the target is the last.  The actions are read back along the
+ * parents and written root first to out_queues[g], the length to out_lens[g]; a result longer than out_width leaves the row
+ * unwritten (RC_SHORTEN_NO_ROOM).  Every neighbour, frontier entry and parent the kernel follows is checked against 1 .. L + 1
+ * and a walk back longer than L ends the game RC_SHORTEN_FAILED. */
+int rc_shorten_bfs(const rc_shorten_t *s, rc_stream_t stream);
+/* rc_shorten_index, rc_shorten_neighbours, rc_shorten_bfs on `stream`. */
+int rc_shorten(const rc_shorten_t *s, rc_stream_t stream);
+
 /* ---- the 6x8x6 representation (csrc/rubiks_env686.hip) -------------------------------------------------------------
  * The reference's second representation (librubiks/cube/cube.py:67-71,311-388): a state is int8[6][8][6], the one-hot colour of
  * the 8 non-centre stickers of each face.  Device form: 48 int8 planes of sticker colour 0..5, plane f*8+p = sticker p of face f

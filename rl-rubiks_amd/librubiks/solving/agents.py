@@ -27,6 +27,7 @@ from librubiks.solving import bfs_device as bd
 from librubiks.solving import egvm_device as ed
 from librubiks.solving import mcts_device as md
 from librubiks.solving import rollout_device as rd
+from librubiks.solving import shorten as sh
 from librubiks.solving.results import BatchResult, QueueTable   # noqa: F401  (also this module's names: callers import them from here)
 from librubiks.utils import TickTock
 
@@ -73,6 +74,24 @@ class Agent:
 
     def __len__(self):
         return self._explored_states
+
+    # `shorten=True` (EGVM, RandomSearch, PolicySearch, ValueSearch): the action queue of every SOLVED game is replaced by the route the
+    # reference's graph shortening (agents.py:597-633, which it applies to MCTS(search_graph=True) only) finds through the states the
+    # queue itself visits (librubiks/solving/shorten.py).  Solved flag, len(agent), status and the times of the search are what they
+    # are without it; an unsolved game's queue -- a best guess, not a solution -- stays.
+    shorten = False
+
+    def _shortened(self, res: BatchResult, states) -> BatchResult:
+        """The assembled result of a `search_batch`, shortened once if the agent was asked to."""
+        return res.shortened(states) if self.shorten else res
+
+    def _shorten_own_queue(self, state: np.ndarray, solved: bool):
+        """`search` under `shorten=True`: the agent's action_queue after a solved search of `state`."""
+        if self.shorten and solved and len(self.action_queue):
+            queues, status = sh.shorten_queues(np.asarray(state)[None], [list(self.action_queue)])
+            if status[0] != sh.OK:
+                raise RuntimeError(f"shortening the action queue failed (status {int(status[0])})")
+            self.action_queue = queues[0]
 
 
 def _unbounded(limit) -> bool:
@@ -1172,12 +1191,12 @@ class _StepAgent(Agent):
         nodes, status EXHAUSTED and 0 seconds.  `nodes`, `iterations` and the queue length of a game are its number of moves.
         """
         if seeds is None and slots is None:
-            return self._search_stepwise(states, time_limit, max_states)
+            return self._shortened(self._search_stepwise(states, time_limit, max_states), states)
         roots = DeviceCubes.of(states)
         if self.kind in rd.RolloutBatch.TABLE_DTYPE:
             seeds = ed.game_seeds(seeds, roots.n)
         time_limit, max_states = Agent.reset(self, time_limit, max_states)
-        return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
+        return self._shortened(self._search_lockstep(roots, time_limit, max_states, seeds, slots), roots)
 
     @no_grad
     def _search_stepwise(self, states, time_limit: float = None, max_states: int = None) -> BatchResult:
@@ -1219,7 +1238,10 @@ class _StepAgent(Agent):
         return BatchResult(solved_h, lengths, steps.astype(np.int64), QueueTable.from_queues(queues), seconds, steps, status, each)
 
     def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
-        return bool(self.search_batch(np.asarray(state)[None], time_limit, max_states).solved[0])
+        res = self.search_batch(np.asarray(state)[None], time_limit, max_states)
+        if self.shorten:
+            self.action_queue = res.queues[0]
+        return bool(res.solved[0])
 
     def _batch_for(self, n_slots: int, queue_width: int) -> "rd.RolloutBatch":
         b, want = self.batch, (n_slots, self.kind, int(self.steps_per_round), bool(self.use_graph))
@@ -1347,6 +1369,11 @@ class RandomSearch(_StepAgent):
     """Uniformly random moves from np.random (reference agents.py:82-90); one draw per running game per step."""
     kind = "random"
 
+    def __init__(self, shorten: bool = False):
+        """shorten: solved games return the shortest route through the states their walk visited (see `Agent.shorten`)."""
+        super().__init__()
+        self.shorten = bool(shorten)
+
     def _actions(self, cubes, running):
         a = torch.from_numpy(np.random.randint(12, size=cubes.n).astype(np.uint8)).to(cubes.soa.device)
         return _pad16(a)
@@ -1356,13 +1383,16 @@ class RandomSearch(_StepAgent):
 
 
 class _DeepStepAgent(_StepAgent, DeepAgent):
-    def __init__(self, net, net_dtype=F32_SPLIT, deterministic: bool = False, use_graph: bool = True, steps_per_round: int = 8):
+    def __init__(self, net, net_dtype=F32_SPLIT, deterministic: bool = False, use_graph: bool = True, steps_per_round: int = 8,
+                 shorten: bool = False):
         """deterministic: as for `MCTS` -- one layer plan of the split engine for every row count, so a game of a lock-step search
         (`search_batch` with `seeds` or `slots`) does not depend on which other games share its batch.
         use_graph, steps_per_round: the lock-step search replays a round of that many (network pass, move) pairs as one
-        captured graph."""
+        captured graph.
+        shorten: solved games return the shortest route through the states they visited (see `Agent.shorten`)."""
         DeepAgent.__init__(self, net, net_dtype, deterministic)
         self.use_graph, self.steps_per_round = use_graph, steps_per_round
+        self.shorten = bool(shorten)
         self._engine = None
 
     def reset(self, time_limit, max_states):
@@ -1433,13 +1463,16 @@ class EGVM(DeepAgent):
     """
 
     def __init__(self, net, epsilon: float, workers: int, depth: int, net_dtype=F32_SPLIT, deterministic: bool = False,
-                 use_graph: bool = True):
+                 use_graph: bool = True, shorten: bool = False):
         """deterministic: as for `MCTS` -- one layer plan of the split engine for every row count, so a game of a batched search
         (`search_batch` with `seeds` or `slots`) does not depend on which other games share its batch.
-        use_graph: the batched search replays a round (D network passes and depth steps) as one captured graph."""
+        use_graph: the batched search replays a round (D network passes and depth steps) as one captured graph.
+        shorten: a solved game returns the shortest route through the states its queue visited instead of the queue itself, which
+        strings together one epsilon-greedy path prefix per round and so wanders through states it has been in (see `Agent.shorten`)."""
         super().__init__(net, net_dtype, deterministic)
         self.epsilon, self.workers, self.depth = epsilon, workers, depth
         self.use_graph = use_graph
+        self.shorten = bool(shorten)
         self.batch = None
         self.batch_stats = None
 
@@ -1451,6 +1484,11 @@ class EGVM(DeepAgent):
         return f"EGVM (e={self.epsilon}, w={self.workers}, d={self.depth})"
 
     def search(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
+        ok = self._search_raw(state, time_limit, max_states)
+        self._shorten_own_queue(state, ok)
+        return ok
+
+    def _search_raw(self, state: np.ndarray, time_limit: float = None, max_states: int = None) -> bool:
         rng = np.random.get_state()
         ok = self._search(state, time_limit, max_states)
         if self._overflowed(self._engine):   # the split engine could not represent an activation: the same search (same draws) in fp32
@@ -1515,11 +1553,11 @@ class EGVM(DeepAgent):
         nodes, status EXHAUSTED and 0 seconds.  `BatchResult.iterations` is the number of rounds per game.
         """
         if seeds is None and slots is None:
-            return self._search_serial(states, time_limit, max_states)
+            return self._shortened(self._search_serial(states, time_limit, max_states), states)
         roots = DeviceCubes.of(states)
         seeds = ed.game_seeds(seeds, roots.n)
         time_limit, max_states = self.reset(time_limit, max_states)
-        return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
+        return self._shortened(self._search_lockstep(roots, time_limit, max_states, seeds, slots), roots)
 
     def _batch_for(self, n_slots: int, queue_width: int) -> "ed.EGVMBatch":
         b = self.batch
@@ -1644,7 +1682,7 @@ class EGVM(DeepAgent):
         tt = TickTock()
         tt.tick()
         for s in states:
-            ok = self.search(s, time_limit, max_states)
+            ok = self._search_raw(s, time_limit, max_states)
             solved.append(ok), lengths.append(len(self.action_queue) if ok else -1)
             nodes.append(len(self)), queues.append(self.action_queue)
         solved = np.array(solved)

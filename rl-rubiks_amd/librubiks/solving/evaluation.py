@@ -41,6 +41,12 @@ class Evaluator:
         ones handing their place to waiting games (continuous batching); `max_time`, if given, then bounds the whole pool at
         max_time x len(depths).  Agents that draw random numbers then give every game a stream of its own, seeded by one
         draw from the global stream after the scrambles (`search_batch(seeds=None)`).
+
+        Solution lengths ("mean turns to complete", the median and the distribution) are `BatchResult.lengths` as the agent returns
+        them.  An agent built with `shorten=True` (EGVM, RandomSearch, PolicySearch, ValueSearch) returns, for every solved game, the
+        shortest route through the states its queue visited, so its "mean turns" measure the solution the agent found and not the
+        length of the walk that found it; the share of solved games, states seen and play times are the same either way (the
+        shortening runs after the search, outside the per-game intervals).
         """
         self.n_games, self.max_time, self.max_states, self.slots = n_games, max_time, max_states, slots
         self.tt = TickTock()

@@ -86,6 +86,31 @@ class BatchResult:
         # around agent.search (evaluation.py:45-52).  Games of one batch share the GPU, so these intervals OVERLAP: their sum is not
         # the batch's wall time (`seconds`).  None: the agent does not record them.
         self.game_seconds = game_seconds
+        # Set by `shortened` on the result it returns: the lengths the search itself found, and the wall seconds of the shortening.
+        self.raw_lengths, self.shorten_seconds = None, None
+
+    def shortened(self, states, budget_bytes: int = None) -> "BatchResult":
+        """
+        The result with every SOLVED game's queue replaced by the route the reference's graph shortening (agents.py:597-633 of
+        the reference) finds through the states the queue visits (librubiks/solving/shorten.py): same end state, never longer,
+        a function of the game alone.  `states`: the scrambles the search was given ((n, 20) int8 or DeviceCubes).  Unsolved
+        games keep their queues (a best guess, not a solution).  `queues` and `lengths` are the shortened ones, `raw_lengths`
+        what the search returned, `shorten_seconds` the wall time this took; `solved`, `nodes`, `status`, `iterations`,
+        `seconds` and `game_seconds` are the search's.
+        """
+        import time
+
+        from librubiks.solving import shorten as sh
+        t0 = time.perf_counter()
+        solved = np.asarray(self.solved, dtype=bool)
+        queues, status = sh.shorten_queues(states, self.queues, select=solved & (self.queues.lengths() > 0), budget_bytes=budget_bytes)
+        bad = np.flatnonzero((status != sh.OK) & (status != sh.SKIPPED))
+        if len(bad):
+            raise RuntimeError(f"shortening failed for games {bad[:8].tolist()}: {[sh.STATUS_NAMES[int(s)] for s in status[bad[:8]]]}")
+        lengths = np.where(solved, queues.lengths(), self.lengths).astype(np.asarray(self.lengths).dtype)
+        out = BatchResult(self.solved, lengths, self.nodes, queues, self.seconds, self.iterations, self.status, self.game_seconds)
+        out.raw_lengths, out.shorten_seconds = np.asarray(self.lengths).copy(), time.perf_counter() - t0
+        return out
 
     @property
     def states_per_sec(self) -> float:
