@@ -2,6 +2,7 @@
 // the one-hot encoding (the one-hot A fragments of the MFMAs are generated from the cube codes, so the (n x 480) one-hot
 // matrix, the K = 480 GEMM and the separate bias + activation pass never exist), the fused head kernels, the
 // activation / reduce passes of the split engine and the ADI target kernel.
+#include <utility>
 #include <atomic>
 
 #include <type_traits>
@@ -769,19 +770,55 @@ __global__ __launch_bounds__(kMfWaves * kWave) void k_first_layer_split(const u8
 // -- 20 fp32 additions per output instead of 960 multiply-adds on the matrix cores (k_first_layer_split: 60 k-steps of
 // mostly-zero one-hot fragments, VALU-bound on building those fragments), in plain fp32 from the fp32 table (no hi / lo split of
 // the weights: the sum is exact to fp32 rounding, in the fixed order j = 0 .. 19 behind the bias -- whatever the form below).
-// A workgroup owns 64 columns: its slice of the table, [480][64] fp32 = 120 KiB, lives in LDS.  A lane takes C adjacent columns
-// of one state (C / 4 ds_read_b128 per cubie; with C = 4 the 16 lanes of a state read the 256 bytes of a row, all 64 banks once),
-// a wave 64 C / 64 states at a time; the codes of the next states are requested while these are summed.  Like every elementwise
-// part of the network the loop is bound by instruction ISSUE (profiles/r6_input_layer_ab.txt: stores, LDS reads, activation each
-// cost their share of instructions, no resource is full), so the two forms trade per-output overhead against granularity:
-//   <16 waves, C = 4>: four waves per SIMD, units of 4 states -- small batches (352 rows: 9 us);
-//   < 8 waves, C = 8>: half the code loads, address computations and stores per output -- large batches (11 264 rows: 95 us).
+// A workgroup owns 64 columns: its slice of the table, [480][64] fp32 = 120 KiB, lives in LDS (one workgroup per CU).  Two forms
+// behind one entry point, the same additions in the same order and so the same bits:
+//   <16 waves, C = 4>: a lane takes four adjacent columns of one state, one ds_read_b128 per table row (the sixteen lanes of a state
+//     read the 256 bytes of a row, all 64 banks once); a wave four states at a time, the codes of the next four requested while these
+//     are summed, all reads of half a state before its additions.  Four waves per SIMD, units of 4 states: small batches (352 rows: 7 us).
+//   <12 waves, C = 8>: a lane takes two groups of four columns that are 32 columns apart -- two reads per row that no lane group of
+//     ds_read_b128 sends to one bank twice -- and swaps one group with its neighbour lane before it stores sixteen bytes of hi and of lo
+//     halves; a wave eight states at a time as a rolling pipeline: four rows of reads in flight ahead of the additions across the end
+//     of a state, the codes in registers two passes ahead and the map entry three, no wait in the loop that drains the stores.  Half the
+//     code loads and stores per output: large batches.
+// What bounds the eight-column form (profiles/r8_input_layer_ab.txt): at the MCTS step's shape it takes 61 us, 1.5 us per 64 rows
+// of a workgroup, where it took 76 us (1.85) with all reads before all additions.  Its ~260 vector instructions per wave and pass
+// are ~1.0 us of the SIMDs' time, its LDS reads ~0.5 us now that they are free of conflicts (SQ_LDS_BANK_CONFLICT 0, half the
+// active LDS cycles), its stores ~0.7 us of HBM time: the vector pipe is the nearest limit and the loop runs at about 0.7 of it.
+// Neither more rows in flight (2 .. 8: within 1.5 us) nor leaving out a part moves it by that part's share (no activation: -12 us,
+// no table reads: -7 us in diagnostic builds),
+// so what is left is issue: 21 one-byte code loads, 40 reads, ~40 counted waits per wave and pass between the vector instructions.
 // =================================================================================================
 constexpr int kGaCols = 64, kGaRows = 480;
 #ifndef RUBIKS_GATHER_ABLATE   // diagnostic builds (WRONG RESULTS): 1 no stores, 2 no LDS reads, 4 no code loads, 8 no activation
 #define RUBIKS_GATHER_ABLATE 0
 #endif
+// The eight-column form: twelve waves per workgroup (three per SIMD at its 130 .. 137 registers; on one box 58.8 us at the MCTS step's
+// shape against 62.1 with eight and 73.5 before the pipeline) and four table rows in flight ahead of the additions (2, 6 and 8 rows: within 1.5 us of it);
+// profiles/r8_input_layer_ab.txt.
+constexpr int kGaWideWaves = 12, kGaAhead = 4;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+// A state's twenty codes as twenty named registers (as an array the three sets of the pipelined form below end up as one wide vector
+// that the loop carries whole: its zero-extended bytes are then widened at the loop's end, which waits for the codes just requested).
+#define RC_GA_PLANES(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19)
+struct GaCodes {
+#define RC_GA_FIELD(j) u32 c##j;
+    RC_GA_PLANES(RC_GA_FIELD)
+#undef RC_GA_FIELD
+    template <int J> __device__ __forceinline__ u32 &at() {
+        static_assert(J >= 0 && J < kPlanes, "one code per cubie");
+#define RC_GA_PICK(j) if constexpr (J == j) return c##j; else
+        RC_GA_PLANES(RC_GA_PICK) return c0;
+#undef RC_GA_PICK
+    }
+    template <int J> __device__ __forceinline__ u32 at() const { return const_cast<GaCodes *>(this)->template at<J>(); }
+};
+#define RC_INLINE __attribute__((always_inline))   // on a lambda: inlined before anything else looks at the arrays it is handed
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): the index is a constant from the start (a register array indexed by
+// the counter of a loop that is unrolled later is first turned into one wide vector, which the loop then carries as a whole)
+template <class F, int... I> __device__ __forceinline__ void static_for_each(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void static_for(F &&f) { static_for_each(f, std::make_integer_sequence<int, N>{}); }
 
 // MAP: output row r is the layer of state src_map[r], for r < *rows_dev <= n only (the packed rows of an MCTS step).  The grid is
 // the one the host chose from n; the kernel shares the rows that exist among its row groups by the host's own rule.
@@ -792,7 +829,6 @@ __global__ __launch_bounds__(WAVES * kWave) void k_first_layer_gather(const u8 *
                                                                      int *__restrict__ range_flag, const u32 *__restrict__ rows_dev,
                                                                      const int *__restrict__ src_map) {
     static_assert(C == 4 || C == 8, "4 or 8 columns per lane");
-    constexpr int R = C / 4;                  // 16-byte reads per table row and lane
     constexpr u32 kLanes = kGaCols / C;       // lanes per state
     constexpr u32 kStates = kWave / kLanes;   // states per wave and pass
     extern __shared__ __attribute__((aligned(256))) unsigned char lds[];   // [480][64] fp32
@@ -808,99 +844,215 @@ __global__ __launch_bounds__(WAVES * kWave) void k_first_layer_gather(const u8 *
     const size_t row_lo = (size_t)rg * rows_per_block;
     if (row_lo >= n) return;
     const size_t row_hi = (row_lo + rows_per_block < n) ? row_lo + rows_per_block : n;
-    {   // the slice: 480 rows x 16 chunks of 16 B = 7 680 chunks, four requests in flight per thread at a time
-        constexpr u32 kChunks = kGaRows * (kGaCols / 4), kThreads = WAVES * kWave, kBatch = 4;
-        for (u32 i0 = tid; i0 < kChunks; i0 += kBatch * kThreads) {
+    {   // the slice: 480 rows x 16 chunks of 16 B = 7 680 chunks.  Whole rounds of the workgroup's threads carry no guard (their
+        // batches stay in registers: a guarded batch made the compiler keep it in private memory), the rest is one guarded chunk.
+        constexpr u32 kChunks = kGaRows * (kGaCols / 4), kThreads = WAVES * kWave, kRounds = kChunks / kThreads, kBatch = 5;
+        const float4 *src = w_rows + ct * (kGaCols / 4);
+        const auto chunk = [&](u32 i) { return src[(size_t)(i >> 4) * (H / 4) + (i & 15)]; };
+#pragma unroll
+        for (u32 r0 = 0; r0 < kRounds; r0 += kBatch) {
             float4 tmp[kBatch];
 #pragma unroll
-            for (u32 b = 0; b < kBatch; ++b) {
-                const u32 i = i0 + b * kThreads;
-                if (i < kChunks) tmp[b] = w_rows[(size_t)(i >> 4) * (H / 4) + ct * (kGaCols / 4) + (i & 15)];
-            }
+            for (u32 b = 0; b < kBatch; ++b)
+                if (r0 + b < kRounds) tmp[b] = chunk(tid + (r0 + b) * kThreads);
 #pragma unroll
-            for (u32 b = 0; b < kBatch; ++b) {
-                const u32 i = i0 + b * kThreads;
-                if (i < kChunks) reinterpret_cast<float4 *>(lds)[i] = tmp[b];
-            }
+            for (u32 b = 0; b < kBatch; ++b)
+                if (r0 + b < kRounds) reinterpret_cast<float4 *>(lds)[tid + (r0 + b) * kThreads] = tmp[b];
         }
+        if (kChunks % kThreads != 0 && tid < kChunks % kThreads) reinterpret_cast<float4 *>(lds)[tid + kRounds * kThreads] = chunk(tid + kRounds * kThreads);
     }
-    const u32 u = lane % kLanes, sub = lane / kLanes;   // the lane's columns of the tile: C u .. C u + C - 1; its state among the wave's
-    const u32 col = ct * kGaCols + C * u;
-    float4 b4[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) b4[r] = *reinterpret_cast<const float4 *>(bias + col + 4 * r);
+    const u32 u = lane % kLanes, sub = lane / kLanes;   // the lane among its state's, the state among the wave's
     bool out_of_range = false;
-    // The codes: plane j of state t is byte j stride + t of the SoA block -- a buffer load with the state in the vector offset and the
-    // plane in the scalar offset, no 64-bit address arithmetic per byte.  Rows past the end are clamped (computed, not stored).
-    const __amdgpu_buffer_rsrc_t planes = __builtin_amdgcn_make_buffer_rsrc((void *)soa, 0, (int)(u32)(kPlanes * stride), 0x00020000);
-    const u32 last = (u32)(n - 1), pitch = (u32)stride;
-    auto codes_of = [&](size_t t, u32 (&c)[kPlanes]) {
-        u32 tv = t < n ? (u32)t : last;
-        if (MAP) tv = min((u32)src_map[tv], last_state);
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j) c[j] = (RUBIKS_GATHER_ABLATE & 4) ? (tv + j) % 24u : (u32)__builtin_amdgcn_raw_buffer_load_b8(planes, tv, (u32)j * pitch, 0);
-    };
-    // row (24 j + code) of the slice at byte (24 j + code) 256 + 4 C u: the code shifted onto one of two bases, the cubie (and the
-    // lane's second 16 bytes) in the instruction's offset field (16 bits: cubies 0 .. 10 on the first base, 11 .. 19 on the second)
-    const u32 base0 = u * (4 * C), base1 = u * (4 * C) + 11 * 24 * (kGaCols * 4);
-    __syncthreads();
+    const u32 last = (u32)(n - 1);                      // rows past the end are clamped to it: computed, not stored
     constexpr size_t kStep = (size_t)WAVES * kStates;   // states per pass of the workgroup
     size_t t = row_lo + (size_t)wave * kStates + sub;
-    u32 code[kPlanes], code_next[kPlanes];
-    codes_of(t, code);
-    for (size_t t0 = row_lo + (size_t)wave * kStates; t0 < row_hi; t0 += kStep, t += kStep) {
-        const bool more = t0 + kStep < row_hi;        // wave-uniform
-        // the rows are requested a batch at a time before the first of them is added (left to itself the compiler waits for each read
-        // in turn: an LDS latency per row), the next states' codes in between, the additions in the order j = 0 .. 19
-        f32x2 acc[2 * R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[2 * r] = f32x2{b4[r].x, b4[r].y}, acc[2 * r + 1] = f32x2{b4[r].z, b4[r].w};
-        constexpr int kBatch = 10 / R;
-#pragma unroll
-        for (int part = 0; part < kPlanes / kBatch; ++part) {
-            float4 v[kBatch][R];
-#pragma unroll
-            for (int i = 0; i < kBatch; ++i) {
-                const int j = part * kBatch + i;
-                const u32 at = (code[j] << 8) + (j < 11 ? base0 : base1);   // (codes are 0 .. 23; a byte beyond would read zeros past the slice, never fault)
-                const unsigned char *rowp = lds + at + (j < 11 ? j : j - 11) * 24 * (kGaCols * 4);
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    v[i][r] = (RUBIKS_GATHER_ABLATE & 2) ? make_float4(__uint_as_float(at), 1.f, 2.f, 3.f) : *reinterpret_cast<const float4 *>(rowp + 16 * r);
+    if constexpr (C == 8) {
+        // The eight-column form as a rolling pipeline.  A lane's two 16-byte slots of a table row are NOT adjacent: slot s = u ^ 8 p
+        // first, s ^ 8 second, p = (u ^ state) & 1 -- inside every lane group of ds_read_b128 the sixteen lanes then read the sixteen
+        // slots of the 256-byte bank row once (adjacent slots put two states of a group on the same eight slots: every read 2-way).
+        // The lane sums columns 4 s .. 4 s + 3 and 4 (s ^ 8) .. + 3; its neighbour u ^ 1 has the other p, so the second group of one
+        // is the columns next to the first group of the other: they swap it through DPP after the split and each lane stores the
+        // sixteen bytes of hi halves and of lo halves of columns 32 p + 4 (u & 6) .. + 7.
+        // kAhead table rows (2 kAhead reads) are in flight while a row is added, across the end of a state: the first rows of the next
+        // state are requested before the last additions, the activation, the split and the stores of this one.  The codes are in
+        // registers two passes ahead and the map entry three, requested before the pass's stores, so every wait on them is a counted
+        // one that leaves the stores (and the newer requests) outstanding.  Three sets of codes take turns: no register copies.
+        constexpr int kAhead = kGaAhead;
+        const u32 p = (u ^ sub) & 1u, slot = u ^ (8u * p);
+        const u32 lane0 = 16u * slot;
+        const u32 col_k = ct * kGaCols + 4 * slot, col_s = ct * kGaCols + 4 * (slot ^ 8u);   // the columns kept / sent to the neighbour
+        const float4 bias_k = *reinterpret_cast<const float4 *>(bias + col_k), bias_s = *reinterpret_cast<const float4 *>(bias + col_s);
+        const u32 row_bytes = H * 4, out_at = sub * row_bytes + (ct * kGaCols + 32u * p + 4u * (u & 6u)) * 2;   // row pitch 2 H halves; the lane's bytes in its pass
+        const bool odd = u & 1u;
+        // state (or packed row) of the wave's pass `ahead` passes on, clamped to the last one exactly as the rows past the end are
+        const auto row_of = [&](size_t ahead) RC_INLINE {
+            const size_t tt = t + ahead * kStep;
+            return tt < n ? (u32)tt : last;
+        };
+        const auto request = [&](u32 tv, GaCodes &c) RC_INLINE {
+            static_for<kPlanes>([&](auto jc) RC_INLINE {
+                constexpr int j = decltype(jc)::value;
+                c.template at<j>() = (RUBIKS_GATHER_ABLATE & 4) ? (tv + j) % 24u : (u32)(soa + (size_t)j * stride)[tv];   // a uniform base and the state as a 32-bit offset
+            });
+        };
+        // a row's two reads in two operations: the code shifted onto one of two lane bases (cubies 0 .. 10 / 11 .. 19, as above; the
+        // slice's own address included), the second slot 128 bytes above or below the first.  The bases are opaque to the compiler,
+        // which otherwise folds what it knows of their bits into longer sequences.
+        typedef const f32x4 __attribute__((address_space(3))) *SliceRow;
+        u32 first0 = (u32)(size_t)(__attribute__((address_space(3))) unsigned char *)lds + lane0, first1 = first0 + 11 * 24 * (kGaCols * 4);
+        u32 to_second = (lane0 ^ 128u) - lane0;
+        asm("" : "+v"(first0), "+v"(first1), "+v"(to_second));
+        const auto read_row = [&](const GaCodes &c, auto jc, f32x4(&v)[2]) RC_INLINE {
+            constexpr int j = decltype(jc)::value;
+            constexpr u32 imm = (u32)(j < 11 ? j : j - 11) * 24 * (kGaCols * 4);
+            u32 at0 = (c.template at<j>() << 8) + (j < 11 ? first0 : first1);
+            asm("" : "+v"(at0));    // (kept as one sum each: taken apart, the cubie's offset no longer fits the instruction's field)
+            u32 at1 = at0 + to_second;
+            asm("" : "+v"(at1));
+            if (RUBIKS_GATHER_ABLATE & 2) {
+                v[0] = v[1] = f32x4{__uint_as_float(at0 + at1), 1.f, 2.f, 3.f};
+            } else {
+                v[0] = *(SliceRow)(size_t)(at0 + imm);
+                v[1] = *(SliceRow)(size_t)(at1 + imm);
             }
-            __builtin_amdgcn_sched_barrier(0);
-            if (part == 0 && more) codes_of(t + kStep, code_next);
-            __builtin_amdgcn_sched_barrier(0);
+        };
+        const bool any = row_lo + (size_t)wave * kStates < row_hi;   // wave-uniform: the wave has a pass at all
+        GaCodes code_a, code_b, code_c;
+        u32 map_next = 0;
+        if (any) {
+            if (MAP) {
+                request(min((u32)src_map[row_of(0)], last_state), code_a);
+                request(min((u32)src_map[row_of(1)], last_state), code_b);
+                map_next = (u32)src_map[row_of(2)];
+            } else {
+                request(row_of(0), code_a);
+                request(row_of(1), code_b);
+            }
+        }
+        __syncthreads();
+        if (!any) return;
+        f32x4 head[kAhead][2];   // rows 0 .. kAhead - 1 of the coming pass, requested
+        static_for<kAhead>([&](auto ic) RC_INLINE { read_row(code_a, ic, head[decltype(ic)::value]); });
+        size_t t0 = row_lo + (size_t)wave * kStates;
+        const auto pass = [&](const GaCodes &cur, const GaCodes &nxt, GaCodes &far) RC_INLINE {
+            if (MAP) {   // (the map entry first: the wait for it next pass then leaves the codes behind it outstanding, stored or not)
+                const u32 state = min(map_next, last_state);
+                map_next = (u32)src_map[row_of(3)];
+                request(state, far);
+            } else {
+                request(row_of(2), far);
+            }
+            f32x2 acc[4] = {f32x2{bias_k.x, bias_k.y}, f32x2{bias_k.z, bias_k.w}, f32x2{bias_s.x, bias_s.y}, f32x2{bias_s.z, bias_s.w}};
+            f32x4 v[kPlanes + kAhead][2];
 #pragma unroll
-            for (int i = 0; i < kBatch; ++i)
+            for (int i = 0; i < kAhead; ++i) v[i][0] = head[i][0], v[i][1] = head[i][1];
+            static_for<kPlanes>([&](auto jc) RC_INLINE {
+                constexpr int j = decltype(jc)::value, ja = j + kAhead;
+                if constexpr (ja < kPlanes) read_row(cur, std::integral_constant<int, ja>{}, v[ja]);
+                else read_row(nxt, std::integral_constant<int, ja - kPlanes>{}, v[ja]);    // (past the wave's last pass: a clamped state's rows, unused)
+                __builtin_amdgcn_sched_barrier(0);
+                acc[0] += v[j][0].xy;
+                acc[1] += v[j][0].zw;
+                acc[2] += v[j][1].xy;
+                acc[3] += v[j][1].zw;
+                __builtin_amdgcn_sched_barrier(0);
+            });
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    acc[2 * r] += f32x2{v[i][r].x, v[i][r].y};
-                    acc[2 * r + 1] += f32x2{v[i][r].z, v[i][r].w};
+            for (int i = 0; i < kAhead; ++i) head[i][0] = v[kPlanes + i][0], head[i][1] = v[kPlanes + i][1];
+            bool bad = false;
+            SplitPair sp[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (!(RUBIKS_GATHER_ABLATE & 8)) acc[q] = act_value2<ACT>(acc[q], alpha);
+                bad |= !(fabsf(acc[q].x) <= 65504.0f);
+                bad |= !(fabsf(acc[q].y) <= 65504.0f);
+                sp[q] = split_pair(acc[q].x, acc[q].y);
+            }
+            constexpr int kSwapPairs = 0xB1;   // quad_perm [1, 0, 3, 2]
+            const u32 n_hi0 = (u32)__builtin_amdgcn_mov_dpp((int)sp[2].hi, kSwapPairs, 0xF, 0xF, true), n_hi1 = (u32)__builtin_amdgcn_mov_dpp((int)sp[3].hi, kSwapPairs, 0xF, 0xF, true);
+            const u32 n_lo0 = (u32)__builtin_amdgcn_mov_dpp((int)sp[2].lo, kSwapPairs, 0xF, 0xF, true), n_lo1 = (u32)__builtin_amdgcn_mov_dpp((int)sp[3].lo, kSwapPairs, 0xF, 0xF, true);
+            // The stores go through a buffer resource over the rows of this wave's pass that exist: the hardware drops those of a lane
+            // whose row does not (a pass past the wave's last one has no row at all).  No branch: a pass is one straight line.
+            const u32 rows = (RUBIKS_GATHER_ABLATE & 1) ? 0u : t0 < row_hi ? (u32)min(row_hi - t0, (size_t)kStates) : 0u;
+            const __amdgpu_buffer_rsrc_t pass_rows = __builtin_amdgcn_make_buffer_rsrc(out + t0 * ((size_t)H * 4), 0, (int)(rows * row_bytes), 0x00020000);
+            out_of_range |= bad && sub < rows;
+            const u32x4 his = odd ? u32x4{n_hi0, n_hi1, sp[0].hi, sp[1].hi} : u32x4{sp[0].hi, sp[1].hi, n_hi0, n_hi1};
+            const u32x4 los = odd ? u32x4{n_lo0, n_lo1, sp[0].lo, sp[1].lo} : u32x4{sp[0].lo, sp[1].lo, n_lo0, n_lo1};
+            __builtin_amdgcn_raw_buffer_store_b128(his, pass_rows, out_at, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(los, pass_rows, out_at, row_bytes / 2, 0);
+            t0 += kStep, t += kStep;
+        };
+        // three passes, one set of codes each in turn, are one iteration without a branch inside (a value that another block uses is
+        // widened there, after a wait for it); the last one or two passes of a wave stand behind the loop
+        size_t passes = (row_hi - t0 + kStep - 1) / kStep;
+        for (; passes >= 3; passes -= 3) {
+            pass(code_a, code_b, code_c);
+            pass(code_b, code_c, code_a);
+            pass(code_c, code_a, code_b);
+        }
+        if (passes >= 1) pass(code_a, code_b, code_c);
+        if (passes == 2) pass(code_b, code_c, code_a);
+        if (range_flag && out_of_range) atomicOr(range_flag, 1);
+    } else {
+        // The four-column form: the lane's columns 4 u .. 4 u + 3 of the tile, one read per table row -- the sixteen lanes of a state
+        // read the 256 bytes of a row, all 64 banks once.
+        const u32 col = ct * kGaCols + 4 * u;
+        const float4 b4 = *reinterpret_cast<const float4 *>(bias + col);
+        // The codes: plane j of state t is byte j stride + t of the SoA block -- a buffer load with the state in the vector offset and
+        // the plane in the scalar offset, no 64-bit address arithmetic per byte.
+        const __amdgpu_buffer_rsrc_t planes = __builtin_amdgcn_make_buffer_rsrc((void *)soa, 0, (int)(u32)(kPlanes * stride), 0x00020000);
+        const u32 pitch = (u32)stride;
+        auto codes_of = [&](size_t t, u32 (&c)[kPlanes]) {
+            u32 tv = t < n ? (u32)t : last;
+            if (MAP) tv = min((u32)src_map[tv], last_state);
+#pragma unroll
+            for (int j = 0; j < kPlanes; ++j) c[j] = (RUBIKS_GATHER_ABLATE & 4) ? (tv + j) % 24u : (u32)__builtin_amdgcn_raw_buffer_load_b8(planes, tv, (u32)j * pitch, 0);
+        };
+        // row (24 j + code) of the slice at byte (24 j + code) 256 + 16 u: the code shifted onto one of two bases, the cubie in the
+        // instruction's offset field (16 bits: cubies 0 .. 10 on the first base, 11 .. 19 on the second)
+        const u32 base0 = u * 16, base1 = u * 16 + 11 * 24 * (kGaCols * 4);
+        __syncthreads();
+        u32 code[kPlanes], code_next[kPlanes];
+        codes_of(t, code);
+        for (size_t t0 = row_lo + (size_t)wave * kStates; t0 < row_hi; t0 += kStep, t += kStep) {
+            const bool more = t0 + kStep < row_hi;        // wave-uniform
+            // the rows are requested a batch at a time before the first of them is added (left to itself the compiler waits for each
+            // read in turn: an LDS latency per row), the next states' codes in between, the additions in the order j = 0 .. 19
+            f32x2 acc[2] = {f32x2{b4.x, b4.y}, f32x2{b4.z, b4.w}};
+            constexpr int kBatch = 10;
+#pragma unroll
+            for (int part = 0; part < kPlanes / kBatch; ++part) {
+                float4 v[kBatch];
+#pragma unroll
+                for (int i = 0; i < kBatch; ++i) {
+                    const int j = part * kBatch + i;
+                    const u32 at = (code[j] << 8) + (j < 11 ? base0 : base1);   // (codes are 0 .. 23; a byte beyond would read zeros past the slice, never fault)
+                    const unsigned char *rowp = lds + at + (j < 11 ? j : j - 11) * 24 * (kGaCols * 4);
+                    v[i] = (RUBIKS_GATHER_ABLATE & 2) ? make_float4(__uint_as_float(at), 1.f, 2.f, 3.f) : *reinterpret_cast<const float4 *>(rowp);
                 }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        bool bad = false;
-        SplitPair sp[2 * R];
+                __builtin_amdgcn_sched_barrier(0);
+                if (part == 0 && more) codes_of(t + kStep, code_next);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int p = 0; p < 2 * R; ++p) {
-            if (!(RUBIKS_GATHER_ABLATE & 8)) acc[p] = act_value2<ACT>(acc[p], alpha);
-            bad |= !(fabsf(acc[p].x) <= 65504.0f);
-            bad |= !(fabsf(acc[p].y) <= 65504.0f);
-            sp[p] = split_pair(acc[p].x, acc[p].y);
-        }
-        // 16-byte stores (8-byte stores are bound by their issue, not by bandwidth).  C = 8: the lane's eight hi halves, its eight lo
-        // halves.  C = 4: neighbouring lanes (columns 8 i .. 8 i + 3 and 8 i + 4 .. 8 i + 7 of one state) swap halves through DPP, the even
-        // lane stores the hi halves of both, the odd lane the lo halves of both.
-        const bool live = (RUBIKS_GATHER_ABLATE & 1) ? (t < row_hi && acc[0].x == 1.2345e-30f) : t < row_hi;
-        unsigned char *orow = out + t * ((size_t)H * 4);   // row pitch 2 H halves
-        if (C == 8) {
-            if (live) {
-                out_of_range |= bad;
-                *reinterpret_cast<uint4 *>(orow + (size_t)col * 2) = make_uint4(sp[0].hi, sp[1].hi, sp[2 * R - 2].hi, sp[2 * R - 1].hi);
-                *reinterpret_cast<uint4 *>(orow + ((size_t)H + col) * 2) = make_uint4(sp[0].lo, sp[1].lo, sp[2 * R - 2].lo, sp[2 * R - 1].lo);
+                for (int i = 0; i < kBatch; ++i) {
+                    acc[0] += f32x2{v[i].x, v[i].y};
+                    acc[1] += f32x2{v[i].z, v[i].w};
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-        } else {
+            bool bad = false;
+            SplitPair sp[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                if (!(RUBIKS_GATHER_ABLATE & 8)) acc[p] = act_value2<ACT>(acc[p], alpha);
+                bad |= !(fabsf(acc[p].x) <= 65504.0f);
+                bad |= !(fabsf(acc[p].y) <= 65504.0f);
+                sp[p] = split_pair(acc[p].x, acc[p].y);
+            }
+            // 16-byte stores (8-byte stores are bound by their issue, not by bandwidth): neighbouring lanes (columns 8 i .. 8 i + 3 and
+            // 8 i + 4 .. 8 i + 7 of one state) swap halves through DPP, the even lane stores the hi halves of both, the odd lane the lo halves.
+            const bool live = (RUBIKS_GATHER_ABLATE & 1) ? (t < row_hi && acc[0].x == 1.2345e-30f) : t < row_hi;
+            unsigned char *orow = out + t * ((size_t)H * 4);   // row pitch 2 H halves
             constexpr int kSwapPairs = 0xB1;   // quad_perm [1, 0, 3, 2]
             const u32 n_hi0 = (u32)__builtin_amdgcn_mov_dpp((int)sp[0].hi, kSwapPairs, 0xF, 0xF, true), n_hi1 = (u32)__builtin_amdgcn_mov_dpp((int)sp[1].hi, kSwapPairs, 0xF, 0xF, true);
             const u32 n_lo0 = (u32)__builtin_amdgcn_mov_dpp((int)sp[0].lo, kSwapPairs, 0xF, 0xF, true), n_lo1 = (u32)__builtin_amdgcn_mov_dpp((int)sp[1].lo, kSwapPairs, 0xF, 0xF, true);
@@ -910,13 +1062,13 @@ __global__ __launch_bounds__(WAVES * kWave) void k_first_layer_gather(const u8 *
                 const uint4 both = odd ? make_uint4(n_lo0, n_lo1, sp[0].lo, sp[1].lo) : make_uint4(sp[0].hi, sp[1].hi, n_hi0, n_hi1);
                 *reinterpret_cast<uint4 *>(orow + (odd ? (size_t)H + col - 4 : (size_t)col) * 2) = both;
             }
-        }
-        if (more) {
+            if (more) {
 #pragma unroll
-            for (int j = 0; j < kPlanes; ++j) code[j] = code_next[j];
+                for (int j = 0; j < kPlanes; ++j) code[j] = code_next[j];
+            }
         }
+        if (range_flag && out_of_range) atomicOr(range_flag, 1);
     }
-    if (range_flag && out_of_range) atomicOr(range_flag, 1);
 }
 
 extern "C" int rc_oh_split_f16(const int8_t *soa, size_t n, size_t stride, uint16_t *out, rc_stream_t stream) {
@@ -1074,7 +1226,7 @@ extern "C" int rc_first_layer_split_flag_f16(const int8_t *soa, size_t n, size_t
     return launch_status();
 }
 
-// form: 0 = by batch size, 1 = sixteen waves x four columns per lane, 2 = eight waves x eight columns (tests force each)
+// form: 0 = by batch size, 1 = sixteen waves x four columns per lane, 2 = twelve waves x eight columns (tests force each)
 static int first_layer_gather(const int8_t *soa, size_t n, size_t stride, const float *w_rows, const float *bias, uint16_t *out_hi_lo,
                               size_t H, int activation, float alpha, int32_t *range_flag, const uint32_t *rows_dev, const int32_t *src_map,
                               int form, rc_stream_t stream) {
@@ -1088,10 +1240,10 @@ static int first_layer_gather(const int8_t *soa, size_t n, size_t stride, const 
     const u32 col_tiles = (u32)(H / kGaCols);
     const size_t lds_bytes = (size_t)kGaRows * kGaCols * 4;
     hipStream_t s = (hipStream_t)stream;
-    // small batches: sixteen waves, four columns per lane (units of 4 states); large ones: eight waves, eight columns per lane.
+    // small batches: sixteen waves, four columns per lane (units of 4 states); large ones: twelve waves, eight columns per lane.
     // A state's outputs are the same bits either way (the same additions in the same order).
     const bool wide = form ? form == 2 : n * col_tiles > (size_t)5000 * 64;
-    const u32 waves = wide ? 8 : 16, states = wide ? 8 : 4;
+    const u32 waves = wide ? kGaWideWaves : 16, states = wide ? 8 : 4;
     u32 row_groups = (256 + col_tiles - 1) / col_tiles;   // ~one workgroup per CU (the LDS slice allows no more)
     const u32 rows_per_pass = waves * states;
     const size_t per_group = ceil_div(n, (size_t)row_groups);   // (small batches: units of one wave's states, more workgroups)
@@ -1116,9 +1268,9 @@ static int first_layer_gather(const int8_t *soa, size_t n, size_t stride, const 
 #define RC_LAUNCH_GA_ACT(ACT)                              \
     do {                                                   \
         if (rows_dev) {                                    \
-            if (wide) RC_LAUNCH_GA(ACT, 8, 8, true);       \
+            if (wide) RC_LAUNCH_GA(ACT, kGaWideWaves, 8, true);      \
             else RC_LAUNCH_GA(ACT, 16, 4, true);           \
-        } else if (wide) RC_LAUNCH_GA(ACT, 8, 8, false);   \
+        } else if (wide) RC_LAUNCH_GA(ACT, kGaWideWaves, 8, false);  \
         else RC_LAUNCH_GA(ACT, 16, 4, false);              \
     } while (0)
     if (activation == RC_ACT_ELU) RC_LAUNCH_GA_ACT(RC_ACT_ELU);
