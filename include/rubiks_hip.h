@@ -989,6 +989,83 @@ int rc_shorten_bfs(const rc_shorten_t *s, rc_stream_t stream);
 /* rc_shorten_index, rc_shorten_neighbours, rc_shorten_bfs on `stream`. */
 int rc_shorten(const rc_shorten_t *s, rc_stream_t stream);
 
+/* ---- generalised move patterns in a batch of action sequences (csrc/rubiks_patterns.hip) ------------------------------
+ *
+ * The reference's find_generalized_patterns (librubiks/analysis/pattern_mining.py:8-45): over every contiguous sub-sequence of
+ * length j >= 2 of every sequence, the pattern is the sub-sequence with its faces renamed in order of first appearance, and a
+ * pattern is counted once per sequence that holds it.  A symbol is an action 0 .. 11 (face a / 2 with its direction).  Token of
+ * position k of a sub-sequence, c its symbol: neither c nor its face seen earlier in the sub-sequence -> the next unused letter
+ * (0 = A), upper case; the face seen but not c -> the face's letter, lower case; c itself seen -> the face's letter, upper case
+ * (so F f f is A a A, as in the reference).  Token word: 2 letter + (1 if lower case).  The token at k depends on the symbols up
+ * to k only, so the patterns form a trie and a pattern's count never exceeds its prefix's.
+ *
+ * Level-wise: sequence s owns positions pos_off[s] .. pos_off[s + 1] - 1, one LANE per start (s, i) at position pos_off[s] + i.
+ * A lane carries lane_state (bits 0-11 the symbols seen, bits 12 + 3 f .. the letter of face f) and lane_node, its pattern's node
+ * at the current level, -1 once it is retired.  The node of a pattern of length j is the cell of the key (parent + 1) << 8 |
+ * token + 1 in this level's table node_keys (open addressing, linear probing from rc_patterns_hash(key), 0 = free; the parent is
+ * the lane's node of level j - 1, and 0 at level 2, where every parent is the pattern A).  Keys are compared whole.  seen_keys
+ * holds the keys (node + 1) << 32 | s + 1 in the same way: the lane whose insert creates the key adds 1 to node_count[node].
+ * node_first[node] is the smallest s << 32 | i among the node's lanes.  Both tables are cleared at the start of every level and
+ * the host states their sizes for the level: powers of two >= 2 x the live lanes, so an insert finds a cell; the probe is
+ * bounded by the size all the same and a lane that finds none sets status[s] = RC_PATTERNS_NO_ROOM and retires.  No lane waits
+ * for another: a launch boundary completes everything a later step reads.
+ *
+ * rc_patterns_workspace_bytes(P) with C = rc_patterns_table_cells(P) and r(x) = x rounded up to 256:
+ *   3 r(4 P) + r(8 C) + r(4 C) + r(8 C) + r(8 C) + r(16 P) + 256
+ * (lane_seq, lane_state, lane_node; node_keys, node_count, node_first, seen_keys; out_rows; counters): 28 B per position and
+ * 28 B per cell, 2 .. 4 cells per position, whatever the support. */
+#define RC_PATTERNS_OK 0
+#define RC_PATTERNS_BAD_ACTION 1 /* a byte >= 12 inside the sequence's length: no lane of the sequence ever runs */
+#define RC_PATTERNS_FAILED 2     /* lens[s] or the offsets of s do not fit what the struct states: as above */
+#define RC_PATTERNS_NO_ROOM 3    /* a lane of s found no cell in a table smaller than the header asks for */
+
+typedef struct rc_patterns {
+    uint32_t n_seqs;          /* n >= 1 */
+    uint32_t width;           /* bytes per row of `acts`, >= 1 */
+    uint32_t level;           /* j >= 2: the length of the patterns that rc_patterns_extend / rc_patterns_close work on */
+    uint32_t min_count;       /* nodes below it are not reported and retire their lanes */
+    size_t total_positions;   /* P = pos_off[n] >= 1: rows of the lane arrays */
+    size_t node_cells;        /* cells of node_keys, node_count, node_first used at this level: a power of two >= 2 */
+    size_t seen_cells;        /* cells of seen_keys used at this level: a power of two >= 2 */
+    size_t out_cap;           /* rows of out_rows; a level has at most as many nodes as live lanes, so P is always enough */
+    const uint8_t *acts;      /* [n][width] */
+    const int32_t *lens;      /* [n] moves of sequence s, 0 .. width */
+    const uint64_t *pos_off;  /* [n + 1] prefix sums of lens, made on the host */
+    uint32_t *lane_seq;       /* [P] s of the position (written for every position by rc_patterns_begin) */
+    uint32_t *lane_state;     /* [P] symbols seen and letters given, see above */
+    int32_t *lane_node;       /* [P] node at the current level; -1: retired */
+    uint64_t *node_keys;      /* [node_cells] */
+    uint32_t *node_count;     /* [node_cells] sequences that hold the node's pattern */
+    uint64_t *node_first;     /* [node_cells] smallest s << 32 | i; all ones: free cell */
+    uint64_t *seen_keys;      /* [seen_cells] */
+    uint32_t *out_rows;       /* [out_cap][4] {count, first s, first i, level} of the nodes with count >= min_count, in any order */
+    uint32_t *counters;       /* [4] {live lanes, rows written by this level, rows that found out_rows full, 0} */
+    int32_t *status;          /* [n] RC_PATTERNS_* */
+} rc_patterns_t;
+
+size_t rc_patterns_struct_bytes(void);
+/* Host only.  Cells of a table for `keys` keys: the smallest power of two >= max(2 keys, 2); 0 if keys >= 2^40. */
+size_t rc_patterns_table_cells(size_t keys);
+/* Host only: the formula above; 0 if P >= 2^40. */
+size_t rc_patterns_workspace_bytes(size_t total_positions);
+/* Host only: the cell at which the probe of `key` starts is rc_patterns_hash(key) & (cells - 1). */
+uint64_t rc_patterns_hash(uint64_t key);
+/* Level 1.  status[s] for every sequence (a length outside 0 .. width or offsets that disagree with it: FAILED; else a byte
+ * >= 12 inside the length: BAD_ACTION).  Then lane_seq for every position, and for the positions of the sequences that are OK
+ * the state after the lane's first symbol and node 0 -- every pattern of length 1 is A, so level 1 has one node and is not
+ * counted --, or -1 where the sequence ends before a second symbol; every other position gets -1 and nothing else.
+ * counters = {live lanes, 0, 0, 0}. */
+int rc_patterns_begin(const rc_patterns_t *p, rc_stream_t stream);
+/* Level j = p->level: clears the tables and counters, then every live lane (s, i) reads acts[s][i + j - 1], forms its token,
+ * finds or creates its node and the (node, s) key, counts and records the first occurrence as described above. */
+int rc_patterns_extend(const rc_patterns_t *p, rc_stream_t stream);
+/* After rc_patterns_extend of the same level: appends {count, first s, first i, j} of every node with count >= min_count to
+ * out_rows (counters[1] rows; a row beyond out_cap is counted in counters[2] and not written), retires the lanes whose node
+ * is below min_count or whose sequence has no symbol i + j, and leaves the number of live lanes in counters[0]. */
+int rc_patterns_close(const rc_patterns_t *p, rc_stream_t stream);
+/* rc_patterns_extend, rc_patterns_close on `stream`. */
+int rc_patterns_level(const rc_patterns_t *p, rc_stream_t stream);
+
 /* ---- the 6x8x6 representation (csrc/rubiks_env686.hip) -------------------------------------------------------------
  * The reference's second representation (librubiks/cube/cube.py:67-71,311-388): a state is int8[6][8][6], the one-hot colour of
  * the 8 non-centre stickers of each face.  Device form: 48 int8 planes of sticker colour 0..5, plane f*8+p = sticker p of face f

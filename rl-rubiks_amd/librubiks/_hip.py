@@ -83,8 +83,19 @@ SIGNATURES = {
     # the conv branch of the 6x8x6 ConvNet from the code planes (csrc/rubiks_conv686.hip)
     "rc_conv686_packed_floats": [I, I, I, P, P],
     "rc_conv686_branch": [P, SZ, SZ, P, P, P, SZ, SZ, I, I, ctypes.c_float, P, P],
+    # pattern mining (csrc/rubiks_patterns.hip); no search module imports it, so it is declared here: the struct pointer as void*,
+    # which librubiks/analysis/pattern_mining.py replaces by its typed mirror when it is imported
+    "rc_patterns_struct_bytes": [],
+    "rc_patterns_table_cells": [SZ],
+    "rc_patterns_workspace_bytes": [SZ],
+    "rc_patterns_hash": [ctypes.c_uint64],
+    "rc_patterns_begin": [P, P],
+    "rc_patterns_extend": [P, P],
+    "rc_patterns_close": [P, P],
+    "rc_patterns_level": [P, P],
 }
-_RESTYPES = {"rc_error_string": c_char_p, "rc_split_layer_struct_bytes": c_size_t}
+_RESTYPES = {"rc_error_string": c_char_p, "rc_split_layer_struct_bytes": c_size_t, "rc_patterns_struct_bytes": c_size_t,
+             "rc_patterns_table_cells": c_size_t, "rc_patterns_workspace_bytes": c_size_t, "rc_patterns_hash": ctypes.c_uint64}
 
 _lib = None
 _initialised_devices = set()
