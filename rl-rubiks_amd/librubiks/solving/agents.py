@@ -228,7 +228,6 @@ class BFS(Agent):
         host, ev = batch.snapshot()
         ev.synchronize()
         final = host.numpy().copy()
-        taken = []
         while self.tt.tock() < time_limit:                # (the reference tests the clock before every pop, agents.py:105)
             live = owner >= 0
             ended = live & (final[bb.W_STATUS] != bb.RUNNING)
@@ -238,8 +237,7 @@ class BFS(Agent):
                 break
             if pool.waiting and len(done):
                 # the finished slots' results leave without waiting, then the waiting scrambles are planted there
-                w = final[:, done].copy()
-                taken.append((owner[done].copy(), w, batch.take_queues(done, w[bb.W_QUEUE_LEN].max())))
+                pool.take(done, final, batch)
                 pool.refill(done, plant)
             batch.step(self.steps_per_round)
             host, ev = batch.snapshot()
@@ -249,15 +247,7 @@ class BFS(Agent):
         seconds = self.tt.tock()
         left = np.flatnonzero(owner >= 0)
         pool.sighted(left[final[bb.W_STATUS, left] != bb.RUNNING], seconds)
-        parts = [(games, self._part(w, q[0], q[1])) for games, w, q in taken]
-        if len(left):
-            w = final[:, left]
-            parts.append((owner[left], self._part(w, *batch.take_queues(left, w[bb.W_QUEUE_LEN].max())[:2])))
-        result = BatchResult.merge(pool.n_games, parts, seconds)
-        pool.close(result, seconds, 2)
-        self._explored_states = int(result.nodes[0])
-        self.action_queue = result.queues[0]
-        return result
+        return pool.collect(self, batch, final, seconds, 2)
 
     @staticmethod
     def _part(words: np.ndarray, host: torch.Tensor, ev) -> BatchResult:
@@ -577,6 +567,7 @@ class SlotPool:
         self.next_game = self.S
         self._t_start = np.zeros(n_games)           # per game: when its root was planted ...
         self._t_end = np.full(n_games, np.nan)      # ... and when the host first saw it finished (NaN: not yet)
+        self.taken = []                             # `take`: (games, their words, their queue rows on the way to the host)
 
     @property
     def waiting(self) -> bool:
@@ -605,6 +596,117 @@ class SlotPool:
             result.status[self.next_game:] = exhausted_status
             self._t_start[self.next_game:] = seconds
         result.game_seconds = np.where(np.isnan(self._t_end), seconds, self._t_end) - self._t_start
+
+    # ---- batches whose slots show a block of words and a queue row (BFSBatch, EGVMBatch, RolloutBatch) ----
+    def take(self, done: np.ndarray, words: np.ndarray, batch):
+        """The results of the finished slots `done` leave without waiting (before a `refill` plants there): their columns of
+        `words` (the host's copy of the batch's snapshot) and their queue rows, on the way into pinned memory."""
+        w = words[:, done].copy()
+        self.taken.append((self.owner[done].copy(), w, batch.take_queues(done, w[batch.queue_len_row].max())))
+
+    def collect(self, agent, batch, words: np.ndarray, seconds: float, exhausted_status: int) -> BatchResult:
+        """The search ended after `seconds`: -> the games' results -- what `take` set aside and the slots still occupied, as
+        `words` shows them, through `agent._part(words, queue rows, event)` -- merged and closed; game 0's is the agent's own."""
+        left = np.flatnonzero(self.owner >= 0)
+        parts = [(games, agent._part(w, q[0], q[1])) for games, w, q in self.taken]
+        if len(left):
+            w = words[:, left]
+            parts.append((self.owner[left], agent._part(w, *batch.take_queues(left, w[batch.queue_len_row].max())[:2])))
+        result = BatchResult.merge(self.n_games, parts, seconds)
+        self.close(result, seconds, exhausted_status)
+        agent._explored_states = int(result.nodes[0])
+        agent.action_queue = result.queues[0]
+        return result
+
+
+def lockstep_search(agent, batch, pool: SlotPool, roots: DeviceCubes, time_limit: float, cap: int, played_cap: int, by_states: bool,
+                    streams, rounds_fit: bool = True):
+    """
+    The host's round loop of the lock-step agents (EGVM; RandomSearch, PolicySearch, ValueSearch): the games of `roots` go through
+    the `pool.S` slots of `batch` (an EGVMBatch or a RolloutBatch), one `batch.round(table, cap)` after the other.  Round r + 1's
+    table is drawn from the games' `streams` (None: the agent draws nothing) while round r runs, for the games that have played
+    fewer than `played_cap` moves or rounds (`batch.unit` per round).  A search that is not `by_states` (bounded by time only)
+    widens the queue rows between rounds.  rounds_fit=False (EGVM: max_states below one round): the roots are planted, so that
+    solved scrambles are seen, and no round runs.  What else differs between the families is the batch's to say (`LockstepBatch`).
+    -> the BatchResult, or None where the split engine left half range: the caller repeats the search, which then runs in fp32.
+    """
+    S, owner = pool.S, pool.owner
+    tables = batch.host_tables()                      # two: one is drawn into while the other's round runs
+    views = [None if t is None else t.numpy() for t in tables]
+    played = np.zeros(S, dtype=np.int64)              # moves / rounds queued for the slot's game so far
+    stats = agent.batch_stats = {"rounds": 0, "draw_s": 0.0, "draw_exposed_s": 0.0, "wait_s": 0.0, "device_round_ms": []}
+
+    def draw(into, which):
+        """The next round's draws of the games in slots `which`."""
+        if streams is None:
+            return 0.0
+        t0 = perf_counter()
+        batch.draw_round(streams, owner[which], which, into)
+        dt = perf_counter() - t0
+        stats["draw_s"] += dt
+        return dt
+
+    def adopt(which):
+        if streams is not None:
+            streams.start(owner[which])               # every game's own np.random stream starts when the game is planted
+        played[which] = 0
+
+    def plant(into, first):
+        batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first)
+    agent.tt.tick()
+    batch.reset(roots)                                # the first S scrambles; the others move in as games finish
+    host, ev = batch.snapshot()
+    adopt(np.arange(S))
+    ev.synchronize()
+    final = host.numpy().copy()
+    status = final[0]                                 # (root-solved games are known before the first round.)  A VIEW: see the refill below
+    r = 0
+    if rounds_fit and ((status == ed.RUNNING).any() or pool.waiting):
+        stats["draw_exposed_s"] += draw(views[0], np.flatnonzero(status == ed.RUNNING))
+        while True:
+            if not by_states:
+                batch.grow_queues(batch.width_after(int(played.max()), cap))
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            batch.round(tables[r % 2], cap)
+            t1.record()
+            host, ev = batch.snapshot()
+            live = owner >= 0
+            played[live & (status == ed.RUNNING)] += batch.unit
+            # round r + 1 is drawn while round r runs, for every game that can still be running then: a game always makes a whole
+            # round's draws, so its move t uses draw t of its stream whatever ends the game sooner (the draws of a game that is
+            # over are ones the reference would not have made)
+            draw(views[(r + 1) % 2], np.flatnonzero(live & (status == ed.RUNNING) & (played < played_cap)))
+            t_wait = perf_counter()
+            ev.synchronize()
+            stats["wait_s"] += perf_counter() - t_wait
+            stats["device_round_ms"].append(t0.elapsed_time(t1))
+            stats["rounds"] = r = r + 1
+            final = host.numpy().copy()
+            status = final[0]
+            batch.check_status(status, owner, played, agent)
+            now = agent.tt.tock()
+            ended = live & (status != ed.RUNNING)
+            done = np.flatnonzero(ended)
+            pool.sighted(done, now)
+            if now >= time_limit or not (live & ~ended).any() and not pool.waiting:
+                break
+            if pool.waiting and len(done):
+                # the finished slots' results leave without waiting, then the waiting scrambles are planted there
+                pool.take(done, final, batch)
+                fresh = pool.refill(done, plant)
+                adopt(fresh)
+                # (`status` is row 0 of `final`: these two writes also edit the block `collect` reads for the slots still occupied)
+                status[done] = ed.EXHAUSTED           # (an empty slot is not played)
+                status[fresh] = ed.RUNNING            # (a solved scramble shows ROOT_SOLVED in the next block; its draws are not used)
+                stats["draw_exposed_s"] += draw(views[r % 2], fresh)   # (r has been incremented: the table of the round about to run)
+    torch.cuda.synchronize()
+    if batch.engine is not None and agent._overflowed(batch.engine):   # the split engine could not represent an activation
+        return None
+    result = pool.collect(agent, batch, final, agent.tt.tock(), ed.EXHAUSTED)
+    if batch.time_limit_exhausts or not rounds_fit:   # (rounds_fit: agents.py:665 is false before the first round)
+        result.status[result.status == ed.RUNNING] = ed.EXHAUSTED   # the time limit ended these
+    return result
 
 
 class MCTSRun(SlotPool):
@@ -1255,99 +1357,16 @@ class _StepAgent(Agent):
 
     @no_grad
     def _search_lockstep(self, roots: DeviceCubes, time_limit: float, max_states: int, seeds, slots) -> BatchResult:
-        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given)."""
+        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given).
+        The host counts a game's moves: a game is drawn for while it has made fewer than `cap`."""
         by_states = not _unbounded(max_states)
         cap = int(max_states) if by_states else DEFAULT_STEP_CAP
         pool = SlotPool(roots.n, slots, self.tt.tock)
-        S, owner = pool.S, pool.owner
-        batch = self._batch_for(S, cap if by_states else min(cap, self.QUEUE_STEPS))
-        K = batch.K
-        streams = ed.GameStreams(seeds) if batch.table is not None else None   # every game's own np.random stream, started when it is planted
-        tables = batch.host_tables()
-        views = [None if t is None else t.numpy() for t in tables]
-        played = np.zeros(S, dtype=np.int64)              # moves queued for the slot's game so far
-        stats = self.batch_stats = {"rounds": 0, "draw_s": 0.0, "draw_exposed_s": 0.0, "wait_s": 0.0, "device_round_ms": []}
-
-        def draw(into, which):
-            """The next round's draws of the games in slots `which`."""
-            if streams is None:
-                return 0.0
-            t0 = perf_counter()
-            rd.draw(streams, owner[which], which, into)
-            dt = perf_counter() - t0
-            stats["draw_s"] += dt
-            return dt
-
-        def adopt(which):
-            if streams is not None:
-                rd.start(streams, owner[which])
-            played[which] = 0
-
-        def plant(into, first):
-            batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first)
-        self.tt.tick()
-        batch.reset(roots)                                # the first S scrambles; the others move in as games finish
-        words = batch.snapshot()
-        adopt(np.arange(S))
-        words[1].synchronize()
-        final = words[0].numpy().copy()
-        status = final[0]                                 # (root-solved games are known before the first round)
-        taken, r = [], 0
-        if (status == rd.RUNNING).any() or pool.waiting:
-            stats["draw_exposed_s"] += draw(views[0], np.flatnonzero(status == rd.RUNNING))
-            while True:
-                if not by_states:
-                    batch.grow_queues(min(cap, int(played.max()) + K))
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record()
-                batch.round(tables[r % 2], cap)
-                t1.record()
-                host, ev = batch.snapshot()
-                live = owner >= 0
-                played[live & (status == rd.RUNNING)] += K
-                # round r + 1 is drawn while round r runs, for every game that can still be running then: a game always makes K
-                # draws per round, so its move t uses draw t of its stream whatever ends the game sooner
-                draw(views[(r + 1) % 2], np.flatnonzero(live & (status == rd.RUNNING) & (played < cap)))
-                t_wait = perf_counter()
-                ev.synchronize()
-                stats["wait_s"] += perf_counter() - t_wait
-                stats["device_round_ms"].append(t0.elapsed_time(t1))
-                stats["rounds"] = r = r + 1
-                final = host.numpy().copy()
-                status = final[0]
-                if (status == rd.QUEUE_FULL).any():
-                    raise _hip.RubiksHipError(f"{self}: the queue row of slot {int(np.argmax(status == rd.QUEUE_FULL))} is full ({batch.Q} bytes)")
-                if (status == rd.BAD_POLICY).any():       # where np.random.choice raises (reference agents.py:140)
-                    raise ValueError(f"{self}: probabilities contain NaN (game {int(owner[np.argmax(status == rd.BAD_POLICY)])})")
-                now = self.tt.tock()
-                ended = live & (status != rd.RUNNING)
-                done = np.flatnonzero(ended)
-                pool.sighted(done, now)
-                if now >= time_limit or not (live & ~ended).any() and not pool.waiting:
-                    break
-                if pool.waiting and len(done):
-                    # the finished slots' results leave without waiting, then the waiting scrambles are planted there
-                    taken.append((owner[done].copy(), final[:, done].copy(), batch.take_queues(done, final[1, done].max())))
-                    fresh = pool.refill(done, plant)
-                    adopt(fresh)
-                    status[done] = rd.EXHAUSTED           # (an empty slot is not played)
-                    status[fresh] = rd.RUNNING            # (a solved scramble shows ROOT_SOLVED in the next block; its draws are not used)
-                    stats["draw_exposed_s"] += draw(views[r % 2], fresh)
-        torch.cuda.synchronize()
-        if batch.engine is not None and self._overflowed(batch.engine):   # the split engine could not represent an activation: the same search (same seeds) in fp32
-            return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
-        seconds = self.tt.tock()
-        left = np.flatnonzero(owner >= 0)
-        parts = [(games, self._part(w, q[0], q[1])) for games, w, q in taken]
-        if len(left):
-            w = final[:, left]
-            parts.append((owner[left], self._part(w, *batch.take_queues(left, w[1].max())[:2])))
-        result = BatchResult.merge(pool.n_games, parts, seconds)
-        result.status[result.status == rd.RUNNING] = rd.EXHAUSTED   # the time limit ended these
-        pool.close(result, seconds, rd.EXHAUSTED)
-        self._explored_states = int(result.nodes[0])
-        self.action_queue = result.queues[0]
-        return result
+        batch = self._batch_for(pool.S, cap if by_states else min(cap, self.QUEUE_STEPS))
+        streams = ed.GameStreams(seeds) if batch.table is not None else None   # (the greedy policy and the value agent draw nothing)
+        res = lockstep_search(self, batch, pool, roots, time_limit, cap, cap, by_states, streams)
+        # (None: the split engine could not represent an activation: the same search, same seeds, in fp32)
+        return self._search_lockstep(roots, time_limit, max_states, seeds, slots) if res is None else res
 
     @staticmethod
     def _part(words: np.ndarray, host: torch.Tensor, ev) -> BatchResult:
@@ -1567,106 +1586,24 @@ class EGVM(DeepAgent):
             torch.cuda.empty_cache()
             b = self.batch = ed.EGVMBatch(n_slots, self.workers, self.depth, queue_width, use_graph=self.use_graph)
         b.set_net(self._search_net(), self.net_dtype)   # every search: `net` may have been trained or replaced since the last one
+        b.set_epsilon(self.epsilon)
         return b
 
     QUEUE_ROUNDS = 64   # queue rows of a search bounded by time only start at this many rounds and double between rounds
 
     @no_grad
     def _search_lockstep(self, roots: DeviceCubes, time_limit: float, max_states: int, seeds: np.ndarray, slots) -> BatchResult:
-        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given)."""
-        W, D = self.workers, self.depth
-        cap = int(max_states)
+        """`search_batch` behind `reset`: both limits are set (one may be `reset`'s stand-in for a limit that was not given).
+        The host counts a game's rounds: a game is drawn for while it has played fewer than `rounds_cap`."""
         by_states = not _unbounded(max_states)
-        rounds_cap = ed.queue_rounds(cap, W, D)           # rounds a game can complete (agents.py:665)
+        rounds_cap = ed.queue_rounds(max_states, self.workers, self.depth)   # rounds a game can complete (agents.py:665)
         # (no round fits: every game is planted at once, so that solved scrambles are seen -- agents.py:661 comes before :665)
         pool = SlotPool(roots.n, slots if rounds_cap >= 1 else None, self.tt.tock)
-        S, owner = pool.S, pool.owner
-        batch = self._batch_for(S, D * max(1, rounds_cap if by_states else self.QUEUE_ROUNDS))
-        cdf0 = ed.choice_cdf(self.epsilon)
-        streams = ed.GameStreams(seeds)                   # every game's own np.random stream, started when the game is planted
-        tables = [torch.full((D, batch.R16), ed.POLICY, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        views = [t.numpy() for t in tables]
-        played = np.zeros(S, dtype=np.int64)              # rounds queued for the slot's game so far
-        stats = self.batch_stats = {"rounds": 0, "draw_s": 0.0, "draw_exposed_s": 0.0, "wait_s": 0.0, "device_round_ms": []}
-
-        def draw(into, which):
-            """The next round's decisions of the games in slots `which`."""
-            t0 = perf_counter()
-            streams.draw(owner[which], which, cdf0, W, D, into, batch.R)
-            dt = perf_counter() - t0
-            stats["draw_s"] += dt
-            return dt
-
-        def adopt(which):
-            streams.start(owner[which])
-            played[which] = 0
-
-        def plant(into, first):
-            batch.plant(_to_device_async(into.astype(np.int32), batch.device), roots, first)
-        self.tt.tick()
-        batch.reset(roots)                                # the first S scrambles; the others move in as games finish
-        words = batch.snapshot()
-        adopt(np.arange(S))
-        words[1].synchronize()
-        status = words[0][0].numpy().copy()               # (root-solved games are known before the first round)
-        taken, r = [], 0
-        final = words[0].numpy().copy()
-        if rounds_cap >= 1 and ((status == ed.RUNNING).any() or pool.waiting):
-            stats["draw_exposed_s"] += draw(views[0], np.flatnonzero(status == ed.RUNNING))
-            while True:
-                if not by_states:
-                    batch.grow_queues(D * int(played.max() + 1))
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record()
-                batch.round(tables[r % 2], cap)
-                t1.record()
-                host, ev = batch.snapshot()
-                live = owner >= 0
-                played[live & (status == ed.RUNNING)] += 1
-                # round r + 1 is drawn while round r runs: for every game that can still be running then (a hit ends it sooner:
-                # those draws are ones the reference would not have made, of a game that is over)
-                go_on = np.flatnonzero(live & (status == ed.RUNNING) & (played < rounds_cap))
-                draw(views[(r + 1) % 2], go_on)
-                t_wait = perf_counter()
-                ev.synchronize()
-                stats["wait_s"] += perf_counter() - t_wait
-                stats["device_round_ms"].append(t0.elapsed_time(t1))
-                stats["rounds"] = r = r + 1
-                final = host.numpy().copy()
-                status = final[0]
-                if (status == ed.QUEUE_FULL).any():
-                    raise _hip.RubiksHipError(f"EGVM: the queue row of slot {int(np.argmax(status == ed.QUEUE_FULL))} is full "
-                                              f"({batch.Q} bytes, {int(played.max())} rounds)")
-                now = self.tt.tock()
-                ended = live & (status != ed.RUNNING)
-                done = np.flatnonzero(ended)
-                pool.sighted(done, now)
-                if now >= time_limit or not (live & ~ended).any() and not pool.waiting:
-                    break
-                if pool.waiting and len(done):
-                    # the finished slots' results leave without waiting, then the waiting scrambles are planted there
-                    taken.append((owner[done].copy(), final[:, done].copy(), batch.take_queues(done, final[2, done].max())))
-                    fresh = pool.refill(done, plant)
-                    adopt(fresh)
-                    status[done] = ed.EXHAUSTED           # (an empty slot is not played)
-                    status[fresh] = ed.RUNNING            # (a solved scramble shows ROOT_SOLVED in the next block; its draws are not used)
-                    stats["draw_exposed_s"] += draw(views[r % 2], fresh)
-        torch.cuda.synchronize()
-        if self._overflowed(batch.engine):   # the split engine could not represent an activation: the same search (same seeds) in fp32
-            return self._search_lockstep(roots, time_limit, max_states, seeds, slots)
-        seconds = self.tt.tock()
-        left = np.flatnonzero(owner >= 0)
-        parts = [(games, self._part(w, q[0], q[1])) for games, w, q in taken]
-        if len(left):
-            w = final[:, left]
-            parts.append((owner[left], self._part(w, *batch.take_queues(left, w[2].max())[:2])))
-        result = BatchResult.merge(pool.n_games, parts, seconds)
-        if rounds_cap < 1:                                # agents.py:665 is false before the first round
-            result.status[result.status == ed.RUNNING] = ed.EXHAUSTED
-        pool.close(result, seconds, ed.EXHAUSTED)
-        self._explored_states = int(result.nodes[0])
-        self.action_queue = result.queues[0]
-        return result
+        batch = self._batch_for(pool.S, self.depth * max(1, rounds_cap if by_states else self.QUEUE_ROUNDS))
+        res = lockstep_search(self, batch, pool, roots, time_limit, int(max_states), rounds_cap, by_states, ed.GameStreams(seeds),
+                              rounds_fit=rounds_cap >= 1)
+        # (None: the split engine could not represent an activation: the same search, same seeds, in fp32)
+        return self._search_lockstep(roots, time_limit, max_states, seeds, slots) if res is None else res
 
     @staticmethod
     def _part(words: np.ndarray, host: torch.Tensor, ev) -> BatchResult:

@@ -17,6 +17,7 @@ import torch
 
 from librubiks import _hip
 from librubiks.cube.device import DeviceCubes
+from librubiks.solving.lockstep_device import pinned_copy, take_queue_rows
 
 RUNNING, SOLVED, CUT, FAILED, ROOT_SOLVED, GRAPH_DONE, EMPTY = 0, 1, 2, 3, 4, 5, 6
 W_STATUS, W_NODES, W_LEVELS, W_QUEUE_LEN, W_LO, W_LEVEL_END, W_MAX_STATES = range(7)
@@ -132,23 +133,15 @@ class BFSBatch:
         for _ in range(k):
             _hip.check(self.lib.rc_bfs_batch_step(b, st), "rc_bfs_batch_step")
 
+    queue_len_row = W_QUEUE_LEN   # the row of a snapshot that holds the queue length
+
     def snapshot(self):
         """(pinned int64 copy [7, S] of the per-slot words status, nodes, levels, queue_len, lo, level_end, max_states; event)."""
-        host = torch.empty((HOST_WORDS, self.S), dtype=torch.int64, pin_memory=True)
-        host.copy_(self.words[:HOST_WORDS], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev
+        return pinned_copy(self.words[:HOST_WORDS])
 
     def take_queues(self, slots: np.ndarray, width: int):
         """Queue rows of `slots`, their first `width` bytes, on their way into pinned memory: (host tensor, event, keep-alive)."""
-        idx = torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).pin_memory().to(self.device, non_blocking=True)
-        rows = self.queues[idx, :max(1, min(int(width), MAX_DEPTH))]
-        host = torch.empty(rows.shape, dtype=torch.uint8, pin_memory=True)
-        host.copy_(rows, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev, (idx, rows)
+        return take_queue_rows(self.queues, slots, min(int(width), MAX_DEPTH))
 
     def node_arrays(self, slot: int, n: int) -> dict:
         """Host copies of the first n node rows of `slot` (for tests)."""

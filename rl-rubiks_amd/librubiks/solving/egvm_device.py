@@ -17,13 +17,11 @@ import numpy as np
 import torch
 
 from librubiks import _hip
-from librubiks.cube.device import DeviceCubes, encode
-from librubiks.model import SplitF32Net, _CubeWindow, make_inference_net, net_fingerprint
-from librubiks.solving.astar_device import NET_CHUNK
+from librubiks.cube.device import DeviceCubes
+from librubiks.solving.lockstep_device import (EXHAUSTED, N_ACT, QUEUE_FULL, ROOT_SOLVED, RUNNING, SOLVED,  # noqa: F401  (also this module's names)
+                                               GameStreams, LockstepBatch, game_seeds)
 
-RUNNING, SOLVED, EXHAUSTED, QUEUE_FULL, ROOT_SOLVED = 0, 1, 2, 3, 4
 POLICY = 255          # decision byte: take the policy's argmax; 0 .. 11: that action
-N_ACT = 12
 MAX_WORKERS, MAX_DEPTH = 0xffff, 0x8000
 
 
@@ -51,154 +49,9 @@ def choice_cdf(epsilon: float) -> float:
     return float(cdf[0])
 
 
-class GameStreams:
-    """
-    The games' np.random streams as the library's host generator runs them (rc_egvm_draw): game g's MT19937 state is that of
-    np.random.RandomState(seeds[g]) from `start(g)` on, and `draw` advances it exactly as the reference's calls advance the
-    RandomState (per depth step `choice(2, W, p=[1 - eps, eps])`, then `randint(0, 12, k)`, agents.py:694-698) -- the same
-    table, the same state afterwards (tests/test_egvm_streams.py) -- at a few nanoseconds per 32-bit output instead of two
-    NumPy calls per depth step and game.
-    """
-
-    def __init__(self, seeds: np.ndarray):
-        self.seeds = np.asarray(seeds, dtype=np.int64)
-        self.keys = np.zeros((len(self.seeds), 624), dtype=np.uint32)
-        self.pos = np.full(len(self.seeds), 624, dtype=np.int32)
-
-    def start(self, games):
-        for g in np.atleast_1d(games):
-            _, key, pos = np.random.RandomState(int(self.seeds[g])).get_state()[:3]
-            self.keys[g], self.pos[g] = key, pos
-
-    def state(self, g: int) -> tuple:
-        """Game g's stream as `RandomState.set_state` takes it."""
-        return ("MT19937", self.keys[g].copy(), int(self.pos[g]), 0, 0.0)
-
-    def draw(self, games, slots, cdf0: float, workers: int, depth: int, table: np.ndarray, n_rows: int):
-        """The next round of `games` (playing in `slots`) into table (uint8 [depth, stride] host array, rows slot W + w)."""
-        games, slots = np.ascontiguousarray(games, dtype=np.int32), np.ascontiguousarray(slots, dtype=np.int32)
-        assert table.dtype == np.uint8 and table.ndim == 2 and table.shape[0] == depth and table.strides == (table.shape[1], 1)
-        _hip.check(_hip.load().rc_egvm_draw(self.keys.ctypes.data, self.pos.ctypes.data, len(self.seeds), games.ctypes.data,
-                                            slots.ctypes.data, len(games), float(cdf0), int(workers), int(depth), table.ctypes.data,
-                                            table.shape[1], int(n_rows)), "rc_egvm_draw")
-
-
-def game_seeds(seeds, n_games: int) -> np.ndarray:
-    """The per-game seeds of a batched search: an integer array [G] as it is, one integer s as
-    RandomState(s).randint(0, 2**31 - 1, size=G), None as one such call on the global stream."""
-    if seeds is None:
-        return np.random.randint(0, 2 ** 31 - 1, size=n_games).astype(np.int64)
-    if np.ndim(seeds) == 0:
-        return np.random.RandomState(int(seeds)).randint(0, 2 ** 31 - 1, size=n_games).astype(np.int64)
-    seeds = np.asarray(seeds)
-    if seeds.shape != (n_games,) or not np.issubdtype(seeds.dtype, np.integer):
-        raise ValueError(f"seeds: one integer or an integer array of shape ({n_games},), got {seeds.dtype} {seeds.shape}")
-    return seeds.astype(np.int64)
-
-
 def queue_rounds(max_states: int, workers: int, depth: int) -> int:
     """Rounds a game can complete under max_states (agents.py:665): its queue row holds that many path prefixes of <= D actions."""
     return int(max_states) // (workers * depth)
-
-
-class LockstepBatch:
-    """What the device batches of the lock-step agents share (EGVMBatch, rollout_device.RolloutBatch): the engine for `net` and the
-    head (12 logits + value) of every row of `self.rows` (a DeviceCubes of `self.R` rows on `self.device`), the captured rounds, the
-    queue rows (`self.queues` [S, Q], named by `self.struct`) and the block of words the host reads per round (`self.words`)."""
-
-    def set_net(self, net, dtype=torch.bfloat16):
-        """Builds the inference engine for `net`; a no-op when the batch already runs exactly these weights."""
-        fp = net_fingerprint(net, dtype)
-        if self.engine is not None and fp == self._net_fp:
-            return
-        self._net_fp = fp
-        self.engine = make_inference_net(net, dtype)
-        self._fused = bool(getattr(self.engine, "supports_cubes", False))
-        rows = min(NET_CHUNK, self.R)
-        self._x1 = self.engine.workspace(rows) if self._fused else None
-        self._oh = None if self._fused else torch.empty((rows, getattr(self.engine, "input_width", 480)), dtype=self.engine.input_dtype, device=self.device)
-        # the head of all rows where it does not come out of the engine as one tensor (several chunks, or logits and values apart)
-        self._head_buf = None if self._fused and self.R <= NET_CHUNK else torch.zeros((self.R, 16), dtype=torch.float32, device=self.device)
-        self._graphs, self._graph_pool = {}, None
-
-    def _head_of(self, lo: int, n: int) -> torch.Tensor:
-        """Engine output for rows lo .. lo + n (lo % 16 == 0): [n, >= 13], 12 logits then the value, float32 or bf16."""
-        eng, rows = self.engine, self.rows
-        if self._fused:
-            x1 = None if self._x1 is None else self._x1[:n]
-            if lo == 0 and n == rows.n:
-                return eng.head_cubes(rows, x1)
-            if isinstance(eng, SplitF32Net):
-                return eng._forward_cubes(rows, eng.layers, lo, n)
-            return eng.head_cubes(_CubeWindow(rows.soa.data_ptr() + lo, n, rows.stride), x1)
-        logits, values = eng(encode(eng, rows, self._oh[:n], lo, n))
-        out = self._head_buf[lo:lo + n]
-        out[:, :N_ACT].copy_(logits)
-        out[:, N_ACT].copy_(values)
-        return out
-
-    def _head(self) -> torch.Tensor:
-        """12 logits + value of every row's current state, chunked as the A* batch chunks its value passes."""
-        if self._fused and self.R <= NET_CHUNK:
-            return self._head_of(0, self.R)
-        for lo in range(0, self.R, NET_CHUNK):
-            n = min(NET_CHUNK, self.R - lo)
-            out = self._head_of(lo, n)
-            if self._fused:
-                self._head_buf[lo:lo + n, :N_ACT + 1].copy_(out[:, :N_ACT + 1])
-        return self._head_buf
-
-    @property
-    def Q(self) -> int:
-        return self.queues.shape[1]
-
-    def _set_queues(self, queues: torch.Tensor):
-        self.queues = queues
-        self.struct.queues, self.struct.queue_width = queues.data_ptr(), queues.shape[1]
-        self._graphs = {}   # (the captured rounds hold the old row address and width)
-
-    def grow_queues(self, width: int):
-        """Queue rows of at least `width` bytes (doubling): between two rounds, contents kept."""
-        if width <= self.Q:
-            return
-        wider = torch.zeros((self.S, max(int(width), 2 * self.Q)), dtype=torch.uint8, device=self.device)
-        wider[:, :self.Q] = self.queues
-        self._set_queues(wider)
-
-    def _run(self, limit: int):
-        """`self._round(limit)`: launched as it is, or -- `use_graph` -- as the replay of its captured graph; the first round of a
-        limit runs eagerly and is then captured (the capture records launches, it does not advance the search)."""
-        if not self.use_graph:
-            return self._round(limit)
-        g = self._graphs.get(limit)
-        if g is not None:
-            return g.replay()
-        self._round(limit)
-        torch.cuda.synchronize()
-        if self._graph_pool is None:
-            self._graph_pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._graph_pool):
-            self._round(limit)
-        self._graphs[limit] = g
-
-    def snapshot(self):
-        """(pinned int64 copy of `words` (per slot: status and the counters), event): the one block the host reads per round."""
-        host = torch.empty(self.words.shape, dtype=torch.int64, pin_memory=True)
-        host.copy_(self.words, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev
-
-    def take_queues(self, slots: np.ndarray, width: int):
-        """Queue rows of `slots`, their first `width` bytes, on their way into pinned memory: (host tensor, event, keep-alive)."""
-        idx = torch.from_numpy(np.ascontiguousarray(slots, dtype=np.int64)).pin_memory().to(self.device, non_blocking=True)
-        rows = self.queues[idx, :max(1, int(width))]
-        host = torch.empty(rows.shape, dtype=torch.uint8, pin_memory=True)
-        host.copy_(rows, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return host, ev, (idx, rows)
 
 
 class EGVMBatch(LockstepBatch):
@@ -237,11 +90,6 @@ class EGVMBatch(LockstepBatch):
         self._graphs, self._graph_pool = {}, None
 
     # ---- search phases ---------------------------------------------------------------------------
-    def reset(self, roots: DeviceCubes):
-        """Slot s starts from roots[s] (roots may hold more scrambles: the rest wait for `plant`)."""
-        assert roots.n >= self.S and self.engine is not None
-        self.plant(torch.arange(self.S, dtype=torch.int32, device=self.device), roots, 0)
-
     def plant(self, slots: torch.Tensor, roots: DeviceCubes, first: int):
         """Slots `slots` (int32 device tensor) restart from roots[first], roots[first + 1], ...; the others are not touched."""
         assert slots.dtype == torch.int32 and slots.is_cuda and slots.is_contiguous() and first + slots.numel() <= roots.n
@@ -266,3 +114,28 @@ class EGVMBatch(LockstepBatch):
         assert decisions.dtype == torch.uint8 and tuple(decisions.shape) == (self.D, self.R16) and self.engine is not None
         self.decisions.copy_(decisions, non_blocking=True)
         self._run(int(max_states))
+
+    # ---- what the host's round loop asks (agents.lockstep_search) ----------------------------------
+    unit = 1                      # the host counts a game's rounds
+    queue_len_row = 2             # the row of `words` that holds the queue length
+    time_limit_exhausts = False   # a game the pool's time limit stops keeps status RUNNING (deliberate by history, unlike RolloutBatch)
+
+    def set_epsilon(self, epsilon: float):
+        self.cdf0 = choice_cdf(epsilon)
+
+    def host_tables(self) -> list:
+        """Two pinned host tables for `round`, one to draw into while the other's round runs: new ones per search, so that the
+        columns of slots nobody draws for say POLICY."""
+        return [torch.full((self.D, self.R16), POLICY, dtype=torch.uint8).pin_memory() for _ in range(2)]
+
+    def draw_round(self, streams: GameStreams, games, slots, table: np.ndarray):
+        streams.draw(games, slots, self.cdf0, self.W, self.D, table, self.R)
+
+    def width_after(self, played: int, cap: int) -> int:
+        """Queue bytes that one more round can need after `played` rounds (a search bounded by time only)."""
+        return self.D * (played + 1)
+
+    def check_status(self, status: np.ndarray, owner: np.ndarray, played: np.ndarray, agent):
+        if (status == QUEUE_FULL).any():
+            raise _hip.RubiksHipError(f"EGVM: the queue row of slot {int(np.argmax(status == QUEUE_FULL))} is full "
+                                      f"({self.Q} bytes, {int(played.max())} rounds)")

@@ -17,9 +17,10 @@ import torch
 
 from librubiks import _hip
 from librubiks.cube.device import DeviceCubes, _stride_for
-from librubiks.solving.egvm_device import N_ACT, GameStreams, LockstepBatch
+from librubiks.solving.lockstep_device import (EXHAUSTED, N_ACT, QUEUE_FULL, ROOT_SOLVED, RUNNING, SOLVED,  # noqa: F401  (also this module's names)
+                                               GameStreams, LockstepBatch)
 
-RUNNING, SOLVED, EXHAUSTED, QUEUE_FULL, ROOT_SOLVED, BAD_POLICY = 0, 1, 2, 3, 4, 5
+BAD_POLICY = 5        # a slot's status beyond the shared ones: a NaN among the sampled policy's probabilities
 POLICY = 255          # decision byte: ask the network; 0 .. 11: that action
 KINDS = ("random", "greedy", "sampled", "value")
 DRAW_BYTES, DRAW_UNIFORMS = 0, 1   # rc_rollout_draw's modes
@@ -35,17 +36,11 @@ _hip.register({
     "rc_rollout_plant": [POINTER(_RoStruct), c_void_p, c_uint32, c_void_p, c_size_t, c_size_t, c_int, c_void_p],
     "rc_rollout_step_policy": [POINTER(_RoStruct), c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_uint64, c_void_p],
     "rc_rollout_step_value": [POINTER(_RoStruct), c_void_p, c_uint64, c_void_p],
-    "rc_rollout_seed": [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p],
     "rc_rollout_draw": [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_int, c_uint32, c_void_p, c_size_t],
 }, {"rc_rollout_struct_bytes": c_size_t})
 
 
-def start(streams: GameStreams, games):
-    """`GameStreams.start` in the library: the listed games' generators as np.random.RandomState(seed) starts them (a NumPy
-    object per game costs 20 us, which a batch of short games notices)."""
-    games = np.ascontiguousarray(games, dtype=np.int32)
-    _hip.check(_hip.load().rc_rollout_seed(streams.keys.ctypes.data, streams.pos.ctypes.data, len(streams.seeds), games.ctypes.data,
-                                           len(games), streams.seeds.ctypes.data), "rc_rollout_seed")
+start = GameStreams.start   # start(streams, games): the older name of `streams.start(games)`
 
 
 def draw(streams: GameStreams, games, slots, table: np.ndarray):
@@ -104,11 +99,6 @@ class RolloutBatch(LockstepBatch):
         return self._host_tables or [None, None]
 
     # ---- search phases ---------------------------------------------------------------------------
-    def reset(self, roots: DeviceCubes):
-        """Slot s starts from roots[s] (roots may hold more scrambles: the rest wait for `plant`)."""
-        assert roots.n >= self.S
-        self.plant(torch.arange(self.S, dtype=torch.int32, device=self.device), roots, 0)
-
     def plant(self, slots: torch.Tensor, roots: DeviceCubes, first: int):
         """Slots `slots` (int32 device tensor) restart from roots[first], roots[first + 1], ...; the others are not touched."""
         assert slots.dtype == torch.int32 and slots.is_cuda and slots.is_contiguous() and first + slots.numel() <= roots.n
@@ -139,3 +129,19 @@ class RolloutBatch(LockstepBatch):
             assert table.dtype == self.table.dtype and table.shape == self.table.shape
             self.table.copy_(table, non_blocking=True)
         self._run(int(max_steps))
+
+    # ---- what the host's round loop asks (agents.lockstep_search) ----------------------------------
+    unit = property(lambda self: self.K)   # the host counts a game's moves: K per round
+    queue_len_row = 1             # the row of `words` that holds the queue length (`steps`)
+    time_limit_exhausts = True    # a game the pool's time limit stops ends EXHAUSTED
+    draw_round = staticmethod(draw)
+
+    def width_after(self, played: int, cap: int) -> int:
+        """Queue bytes that one more round can need after `played` moves (a search bounded by time only)."""
+        return min(cap, played + self.K)
+
+    def check_status(self, status: np.ndarray, owner: np.ndarray, played: np.ndarray, agent):
+        if (status == QUEUE_FULL).any():
+            raise _hip.RubiksHipError(f"{agent}: the queue row of slot {int(np.argmax(status == QUEUE_FULL))} is full ({self.Q} bytes)")
+        if (status == BAD_POLICY).any():       # where np.random.choice raises (reference agents.py:140)
+            raise ValueError(f"{agent}: probabilities contain NaN (game {int(owner[np.argmax(status == BAD_POLICY)])})")

@@ -137,6 +137,24 @@ def test_no_round_fits(net_gpu):
     assert res.status.tolist() == [ed.ROOT_SOLVED if g == 5 else ed.EXHAUSTED for g in range(6)] and (res.iterations == 0).all()
 
 
+def test_the_time_limit_ends_the_pool_after_its_first_round(net_gpu):
+    """A time limit that has passed when the clock is first looked at, behind round 1: the two games in the slots played one round
+    and stay RUNNING (the pool's time limit is not a game's end here), the four still waiting end as games that never got a slot."""
+    from librubiks.solving import egvm_device as ed
+    np.random.seed(19)
+    states = np.array([oc.scramble(9, True)[0] for _ in range(6)])
+    agent = _agent(net_gpu, 0.375, 2, 2)
+    res = agent.search_batch(states, 1e-9, 4_000, seeds=np.arange(6) + 100, slots=2)       # (1 000 rounds fit: no cap ends a game)
+    print("status", res.status.tolist(), "nodes", res.nodes.tolist(), "game_seconds", res.game_seconds.tolist(), "seconds", res.seconds)
+    assert agent.batch_stats["rounds"] == 1
+    assert not res.solved[2:].any() and (res.nodes[2:] == 0).all() and (res.game_seconds[2:] == 0).all()
+    assert (res.status[2:] == ed.EXHAUSTED).all() and (res.lengths[2:] == -1).all()
+    played = ~res.solved[:2]
+    assert played.any() and (res.status[:2][played] == ed.RUNNING).all() and (res.status[:2][~played] == ed.SOLVED).all()
+    assert (res.nodes[:2][played] == 2 * 2).all() and (res.iterations[:2] == 1).all() and (res.game_seconds[:2] > 0).all()
+    assert res.seconds >= res.game_seconds.max()
+
+
 def test_pooling(net_gpu):
     from librubiks.solving import egvm_device as ed
     _, n, depth_of, solved_at, eps, W, D, cap, _ = MAIN
@@ -209,7 +227,7 @@ def test_captured_rounds(net_gpu):
 def test_chunked_network_passes(net_gpu, trained, monkeypatch):
     """More rows than one network call takes (NET_CHUNK): the head of a step is assembled from several calls, with the same results."""
     from librubiks.model import F32_SPLIT
-    from librubiks.solving import egvm_device as ed
+    from librubiks.solving import lockstep_device as ed   # (where the network passes of both lock-step batches are chunked)
     _, n, depth_of, solved_at, eps, W, D, cap, _ = MAIN
     states, seeds = inputs(MAIN[0], n, depth_of, solved_at)
     whole = _agent(net_gpu, eps, W, D).search_batch(states, None, cap, seeds=seeds)

@@ -132,6 +132,25 @@ def test_oracle_parity(net_gpu, kind, ref_cls):
     assert set(res.status.tolist()) <= {rd.SOLVED, rd.EXHAUSTED, rd.ROOT_SOLVED} and (res.status == rd.EXHAUSTED).any()
 
 
+def test_the_time_limit_ends_the_pool_after_its_first_round(net_gpu):
+    """A time limit that has passed when the clock is first looked at, behind round 1: the two games in the slots made one round's
+    moves and end EXHAUSTED (the time limit ended them), the four still waiting end as games that never got a slot."""
+    from librubiks.solving import rollout_device as rd
+    np.random.seed(19)
+    states = np.array([oc.scramble(9, True)[0] for _ in range(6)])
+    agent = make("greedy", net_gpu, steps_per_round=2)
+    res = agent.search_batch(states, 1e-9, 1_000, slots=2)                    # (500 rounds fit: no cap ends a game)
+    print("status", res.status.tolist(), "nodes", res.nodes.tolist(), "game_seconds", res.game_seconds.tolist(), "seconds", res.seconds)
+    consistent(res)
+    assert agent.batch_stats["rounds"] == 1
+    assert not res.solved[2:].any() and (res.nodes[2:] == 0).all() and (res.game_seconds[2:] == 0).all()
+    assert (res.status[2:] == rd.EXHAUSTED).all()
+    played = ~res.solved[:2]
+    assert played.any() and (res.status[:2][played] == rd.EXHAUSTED).all() and (res.status[:2][~played] == rd.SOLVED).all()
+    assert (res.nodes[:2][played] == 2).all() and (res.game_seconds[:2] > 0).all()
+    assert res.seconds >= res.game_seconds.max()
+
+
 # ---- 3. shapes where the kernels can go wrong -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 def test_every_shape_plays_the_same_games(net_gpu, kind):
