@@ -141,6 +141,7 @@ __global__ __launch_bounds__(WM *WN * 64) void k_split_gemm(GemmArgs g) {
     // (a 64-bit vector add in front of every piece held the wave's issue next to the MFMAs: profiles/r6_gemm_ablation.txt).
     constexpr int DW = T::WAVES;   // waves that issue LDS-DMA: all of them (one wave per SIMD issuing everything: 7.9 -> 9.2 ms, profiles/r6_gemm_ablation.txt)
     constexpr int PA = (T::BM / 8 + DW - 1) / DW, PW = (T::BN / 8 + DW - 1) / DW;
+    static_assert(PA + PW <= kPiecesPerRow * MR, "a wave's LDS-DMA pieces of the next stage are issued kPiecesPerRow at a time behind its MR row fragments");
     u32 src_off[PA + PW];
 #pragma unroll
     for (int i = 0; i < PA + PW; ++i) {

@@ -47,7 +47,7 @@ def _branch(act: str, batchnorm: bool):
     from librubiks.model import ConvNet, ModelConfig, _fold_conv, pack_conv686
     key = (act, batchnorm)
     if key not in _branches:
-        fn = nn.ELU() if act == "elu" else nn.ReLU()
+        fn = nn.ELU(alpha=float(act[3:] or 1.0)) if act.startswith("elu") else nn.ReLU()
         net = fill(ConvNet(ModelConfig(architecture="conv", is2024=False, batchnorm=batchnorm, activation_function=fn))).eval()
         with torch.no_grad():
             convs, last = _fold_conv(net.shared_conv_net)
@@ -64,9 +64,9 @@ def _launch(cubes, w, b, fmt, act, n=None, lo=0, pitch=1024, col0=0, flag=None, 
     dtype = (torch.float32, torch.bfloat16, torch.float16)[fmt]
     width = 2 * pitch if fmt == 2 else pitch
     out = torch.empty((n, width), dtype=dtype, device="cuda") if fill_value is None else torch.full((n, width), fill_value, dtype=dtype, device="cuda")
-    code = {"none": 0, "relu": 1, "elu": 2}[act]
+    code, alpha = (2, float(act[3:] or 1.0)) if act.startswith("elu") else ({"none": 0, "relu": 1}[act], 1.0)   # "elu0.37": ELU(alpha = 0.37)
     _hip.check(_hip.lib().rc_conv686_branch(cubes.soa.data_ptr() + lo, n, cubes.stride, w.data_ptr(), b.data_ptr(), out.data_ptr(), width, col0,
-                                            fmt, code, 1.0, None if flag is None else flag.data_ptr(), _hip.stream_ptr()), "rc_conv686_branch")
+                                            fmt, code, alpha, None if flag is None else flag.data_ptr(), _hip.stream_ptr()), "rc_conv686_branch")
     return out
 
 
@@ -79,7 +79,7 @@ def _value(out, fmt, col0=0):
 
 
 @pytest.mark.parametrize("batchnorm", (True, False))
-@pytest.mark.parametrize("act", ("elu", "relu"))
+@pytest.mark.parametrize("act", ("elu", "relu", "elu0.37"))
 def test_kernel_against_the_float64_expression(act, batchnorm, states):
     from librubiks.cube import DeviceCubes
     from librubiks.model import _conv_branch_torch
