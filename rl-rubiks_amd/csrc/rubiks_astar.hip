@@ -9,7 +9,7 @@
 // outside (compacted over all problems) between the two kernels.
 #include <limits.h>
 
-#include "rubiks_common.h"
+#include "rubiks_keys.h"
 
 namespace rubiks {
 
@@ -97,15 +97,8 @@ __device__ int heap_pop(double *hc, int *hi, int &size) {
 // list (cost 0, index 1), counters, status, solved_idx.  rc_astar_init writes it for every problem, rc_astar_plant for listed slots.
 __device__ void astar_init_problem(const rc_astar_t &a, u32 b, const u8 *__restrict__ roots, size_t stride, size_t col) {
     AStarView v = view_of(a, b);
-    u32 w[4] = {0, 0, 0, 0};
-    bool solved = true;
-#pragma unroll
-    for (int j = 0; j < kPlanes; ++j) {
-        const u32 code = roots[(size_t)j * stride + col] & 31u;
-        key_set(w, j, code);
-        solved &= code == (u32)(u8)kTables.solved[j];
-    }
-    const uint4 key = make_uint4(w[0], w[1], w[2], w[3]);
+    const uint4 key = key_from_column(roots, stride, col);
+    const bool solved = key_is_solved(key);
     v.keys[1] = key;
     v.tab[key_hash(key) & v.mask] = 1;
     v.G[1] = 0;
@@ -136,8 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_astar_plant(rc_astar_t a, const int 
                                                       size_t stride, size_t first_col) {
     const int s = slots[blockIdx.x];
     if (s < 0 || (u32)s >= a.n_problems) return;   // (the whole workgroup: nothing is written for a slot that does not exist)
-    uint4 *tab4 = reinterpret_cast<uint4 *>(a.hash + (size_t)s * a.hash_size);
-    for (u32 i = threadIdx.x; i < a.hash_size / 4; i += kBlock) tab4[i] = make_uint4(0, 0, 0, 0);
+    hash_row_clear(a.hash + (size_t)s * a.hash_size, a.hash_size);
     __syncthreads();
     if (threadIdx.x == 0) astar_init_problem(a, (u32)s, roots, stride, first_col + blockIdx.x);
 }
@@ -184,22 +176,10 @@ __global__ __launch_bounds__(kBlock) void k_astar_pop_expand(rc_astar_t a, u32 m
     // pass 1: children (row 12 p + k = action k on popped parent p) and read-only membership test
     for (int r = tid; r < rows; r += kBlock) {
         const int p = v.popped[r / kA12];
-        const u32 act = (u32)(r % kA12);
-        const uint4 pk = v.keys[p];
-        u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j)
-            key_set(w, j, lut[act * (2 * kCodePad) + (j >= kCorners ? kCodePad : 0) + key_code(pk, j)]);
-        const uint4 ck = make_uint4(w[0], w[1], w[2], w[3]);
+        const uint4 ck = key_turned(v.keys[p], (u32)(r % kA12), lut);
         v.child_keys[r] = ck;
-        u32 h = key_hash(ck) & v.mask;
-        int found = 0;
-        for (;;) {
-            const int s = v.tab[h];
-            if (s == 0) break;
-            if (key_eq(v.keys[s], ck)) { found = s; break; }
-            h = (h + 1) & v.mask;
-        }
+        u32 h;
+        const int found = key_find(v.tab, v.mask, v.keys, ck, h);
         v.child_node[r] = found ? found : -(int)h - 1;   // unseen: remember where the probe stopped
         if (found) atomicMin(&v.claim[found], r);        // first row that reaches an already known state
     }
@@ -208,20 +188,7 @@ __global__ __launch_bounds__(kBlock) void k_astar_pop_expand(rc_astar_t a, u32 m
     for (int r = tid; r < rows; r += kBlock) {
         int cn = v.child_node[r];
         if (cn > 0) continue;
-        const uint4 ck = v.child_keys[r];
-        u32 h = (u32)(-cn - 1);
-        for (;;) {
-            int s = v.tab[h];
-            if (s == 0) {
-                s = atomicCAS(&v.tab[h], 0, -(r + 1));
-                if (s == 0) break;
-            }
-            if (s < 0 && key_eq(v.child_keys[-s - 1], ck)) {
-                atomicMax(&v.tab[h], -(r + 1));   // -(row+1): the larger value is the smaller row
-                break;
-            }
-            h = (h + 1) & v.mask;   // occupied by another state (old node or another pending child)
-        }
+        const u32 h = claim_lowest_row(v.tab, (u32)(-cn - 1), v.mask, -(r + 1), (u32)rows, v.child_keys, v.child_keys[r]);
         v.child_node[r] = -(int)h - 1;
     }
     __syncthreads();
@@ -284,8 +251,7 @@ __global__ __launch_bounds__(kBlock) void k_astar_gather_new(rc_astar_t a, const
     const size_t col0 = (size_t)new_offset[b];
     for (int i = threadIdx.x; i < cnt; i += kBlock) {
         const uint4 k = v.keys[first + i];
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j) out[(size_t)j * stride + col0 + i] = (u8)key_code(k, j);
+        key_to_column(k, out, stride, col0 + i);
     }
 }
 
@@ -306,12 +272,8 @@ __global__ __launch_bounds__(kBlock) void k_astar_push_relax(rc_astar_t a, const
     __syncthreads();
     // win check on the new states only (agents.py:321).  New states are distinct, so at most one of them is the solved cube:
     // the atomicMax elects nothing, it only carries that one index (> 0) to every lane
-    u32 sw[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < kPlanes; ++j) key_set(sw, j, (u32)(u8)kTables.solved[j]);
-    const uint4 solved_key = make_uint4(sw[0], sw[1], sw[2], sw[3]);
     for (int i = tid; i < cnt; i += kBlock)
-        if (key_eq(v.keys[first + i], solved_key)) atomicMax(&s_won, first + i);
+        if (key_is_solved(v.keys[first + i])) atomicMax(&s_won, first + i);
     // open-list pushes in index order (agents.py:315-317); one lane, the heap is a serial structure
     if (tid == 0) {
         int size = a.heap_size[b];

@@ -11,34 +11,21 @@
 // hash slot per probe.  The host reads back five words per chunk and decides commit / stop.
 #include <hipcub/hipcub.hpp>
 
-#include "rubiks_common.h"
+#include "rubiks_keys.h"
 
 namespace rubiks {
 
 constexpr unsigned long long kNone = ~0ull;
 
-constexpr uint4 make_solved_key() {
-    u32 w[4] = {0, 0, 0, 0};
-    for (int j = 0; j < kPlanes; ++j) w[j / 6] |= (u32)(u8)kTables.solved[j] << (5 * (j % 6));
-    return uint4{w[0], w[1], w[2], w[3]};
-}
-
-__device__ __forceinline__ bool is_solved_key(const uint4 &k) {
-    constexpr uint4 s = make_solved_key();
-    return k.x == s.x && k.y == s.y && k.z == s.z && k.w == s.w;
-}
-
 // result words: [0] first solved row, [1] new rows in the chunk, [2] cutoff parent, [3] new rows before
 // the solved row, [4] new rows before the cutoff parent
 __global__ void k_bfs_init(rc_bfs_t b, const u8 *__restrict__ root) {
-    u32 w[4] = {0, 0, 0, 0};
-    for (int j = 0; j < kPlanes; ++j) key_set(w, j, root[j] & 31u);
-    const uint4 key = make_uint4(w[0], w[1], w[2], w[3]);
+    const uint4 key = key_from_column(root, 1, 0);
     reinterpret_cast<uint4 *>(b.keys)[0] = key;
     b.parent[0] = 0;
     b.action[0] = 0;
     b.hash[key_hash(key) & (b.hash_size - 1)] = 1;
-    b.result[0] = is_solved_key(key) ? 0ull : kNone;   // agents.py:100
+    b.result[0] = key_is_solved(key) ? 0ull : kNone;   // agents.py:100
 }
 
 __global__ void k_bfs_begin(rc_bfs_t b, u32 n_parents) {
@@ -61,26 +48,15 @@ __global__ __launch_bounds__(kBlock) void k_bfs_children(rc_bfs_t b, u32 lo, u32
     unsigned long long first_solved = kNone;
     for (u32 r = blockIdx.x * kBlock + threadIdx.x; r < rows; r += gridDim.x * kBlock) {
         const uint4 pk = keys[lo + r / kActions];
-        const u32 act = r % kActions;
-        u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j)
-            key_set(w, j, lut[act * (2 * kCodePad) + (j >= kCorners ? kCodePad : 0) + key_code(pk, j)]);
-        const uint4 ck = make_uint4(w[0], w[1], w[2], w[3]);
+        const uint4 ck = key_turned(pk, r % kActions, lut);
         child_keys[r] = ck;
         int slot_or_node;
-        if (is_solved_key(ck)) {
+        if (key_is_solved(ck)) {
             slot_or_node = 0;   // never stored (agents.py:111-116)
             if (first_solved == kNone) first_solved = r;
         } else {
-            u32 h = key_hash(ck) & mask;
-            int found = 0;
-            for (;;) {
-                const int s = b.hash[h];
-                if (s == 0) break;
-                if (key_eq(keys[s - 1], ck)) { found = s; break; }
-                h = (h + 1) & mask;
-            }
+            u32 h;
+            const int found = key_find(b.hash, mask, keys - 1, ck, h);   // (cell value c is node c - 1)
             slot_or_node = found ? found : -(int)h - 1;
         }
         b.child_slot[r] = slot_or_node;
@@ -95,21 +71,7 @@ __global__ __launch_bounds__(kBlock) void k_bfs_claim(rc_bfs_t b, u32 rows) {
     for (u32 r = blockIdx.x * kBlock + threadIdx.x; r < rows; r += gridDim.x * kBlock) {
         const int cs = b.child_slot[r];
         if (cs >= 0) continue;
-        const uint4 ck = child_keys[r];
-        u32 h = (u32)(-cs - 1);
-        const int mine = -(int)(r + 1);
-        for (;;) {
-            int s = __hip_atomic_load(&b.hash[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (s == 0) {
-                s = atomicCAS(&b.hash[h], 0, mine);
-                if (s == 0) break;
-            }
-            if (s < 0 && key_eq(child_keys[-s - 1], ck)) {
-                atomicMax(&b.hash[h], mine);   // -(row+1): the larger value is the smaller row
-                break;
-            }
-            h = (h + 1) & mask;   // another state (committed node or another pending row)
-        }
+        const u32 h = claim_lowest_row(b.hash, (u32)(-cs - 1), mask, -(int)(r + 1), rows, child_keys, child_keys[r]);
         b.child_slot[r] = -(int)h - 1;
     }
 }

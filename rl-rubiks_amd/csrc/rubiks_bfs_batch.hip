@@ -9,22 +9,11 @@
 // fit its arrays ends RC_BFSB_FAILED.
 #include <hipcub/hipcub.hpp>
 
-#include "rubiks_common.h"
+#include "rubiks_keys.h"
 
 namespace rubiks {
 
 constexpr unsigned long long kNoRow = ~0ull;
-
-constexpr uint4 solved_key() {   // (as make_solved_key of rubiks_bfs.hip)
-    u32 w[4] = {0, 0, 0, 0};
-    for (int j = 0; j < kPlanes; ++j) w[j / 6] |= (u32)(u8)kTables.solved[j] << (5 * (j % 6));
-    return uint4{w[0], w[1], w[2], w[3]};
-}
-
-__device__ __forceinline__ bool key_is_solved(const uint4 &k) {
-    constexpr uint4 s = solved_key();
-    return k.x == s.x && k.y == s.y && k.z == s.z && k.w == s.w;
-}
 
 __device__ __forceinline__ long long &word(const rc_bfs_batch_t &b, int w, u32 s) {
     return reinterpret_cast<long long *>(b.words)[(size_t)w * b.n_slots + s];
@@ -49,9 +38,7 @@ __global__ __launch_bounds__(kBlock) void k_bfsb_plant(rc_bfs_batch_t b, const i
     const int si = slots[blockIdx.x];
     if (si < 0 || (u32)si >= b.n_slots) return;   // (the whole workgroup: nothing is written for a slot that does not exist)
     const u32 s = (u32)si;
-    u32 w[4] = {0, 0, 0, 0};
-    for (int j = 0; j < kPlanes; ++j) key_set(w, j, roots[(size_t)j * stride + first_col + blockIdx.x] & 31u);
-    const uint4 key = make_uint4(w[0], w[1], w[2], w[3]);
+    const uint4 key = key_from_column(roots, stride, first_col + blockIdx.x);
     const bool solved = key_is_solved(key);
     const u32 root_cell = key_hash(key) & (b.hash_size - 1);
     int4 *cells = reinterpret_cast<int4 *>(b.hash + (size_t)s * b.hash_size);   // (hash_size >= 32: whole int4s)
@@ -123,12 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_bfsb_children(rc_bfs_batch_t b, u32 
         const u32 lo = (u32)word(b, RC_BFSB_W_LO, q.s);
         if ((unsigned long long)lo + q.n_par > b.capacity) continue;   // (k_bfsb_decide fails such a slot)
         const uint4 pk = keys[lo + q.local / kActions];
-        const u32 act = q.local % kActions;
-        u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j)
-            key_set(w, j, lut[act * (2 * kCodePad) + (j >= kCorners ? kCodePad : 0) + key_code(pk, j)]);
-        const uint4 ck = make_uint4(w[0], w[1], w[2], w[3]);
+        const uint4 ck = key_turned(pk, q.local % kActions, lut);
         child_keys[r] = ck;
         int cell_or_node;
         if (key_is_solved(ck)) {
@@ -159,21 +141,7 @@ __global__ __launch_bounds__(kBlock) void k_bfsb_claim(rc_bfs_batch_t b, u32 row
         const int cs = b.child_slot[r];
         if (cs >= 0) continue;
         int *hash = b.hash + (size_t)q.s * b.hash_size;
-        const uint4 ck = child_keys[r];
-        u32 h = (u32)(-cs - 1) & mask;
-        const int mine = -(int)(q.local + 1);
-        for (u32 probes = 0; probes <= mask; ++probes) {
-            int c = __hip_atomic_load(&hash[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (c == 0) {
-                c = atomicCAS(&hash[h], 0, mine);
-                if (c == 0) break;
-            }
-            if (c < 0 && (u32)(-c - 1) < seg && key_eq(child_keys[q.row0 + (u32)(-c - 1)], ck)) {
-                atomicMax(&hash[h], mine);   // -(row+1): the larger value is the smaller row
-                break;
-            }
-            h = (h + 1) & mask;   // another state (committed node or another pending row)
-        }
+        const u32 h = claim_lowest_row(hash, (u32)(-cs - 1), mask, -(int)(q.local + 1), seg, child_keys + q.row0, child_keys[r]);
         b.child_slot[r] = -(int)h - 1;
     }
 }

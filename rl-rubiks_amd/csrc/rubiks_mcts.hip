@@ -12,7 +12,7 @@
 
 #include <type_traits>
 
-#include "rubiks_common.h"
+#include "rubiks_keys.h"
 
 namespace rubiks {
 
@@ -91,19 +91,11 @@ __global__ __launch_bounds__(kBlock) void k_mcts_plant(rc_mcts_t m, const int *_
     stage_to_lds(s_lut, c_tables.lut, sizeof(kTables.lut));
     const u32 t = slots ? (u32)slots[blockIdx.x] : blockIdx.x;
     const size_t col = first_col + blockIdx.x;
-    uint4 *tab4 = reinterpret_cast<uint4 *>(m.hash + (size_t)t * m.hash_size);
-    for (u32 i = threadIdx.x; i < m.hash_size / 4; i += kBlock) tab4[i] = make_uint4(0, 0, 0, 0);
+    hash_row_clear(m.hash + (size_t)t * m.hash_size, m.hash_size);
     __syncthreads();
     if (threadIdx.x == 0) {
-    u32 w[4] = {0, 0, 0, 0};
-    bool solved = true;
-#pragma unroll
-    for (int j = 0; j < kPlanes; ++j) {
-        const u32 code = roots[(size_t)j * stride + col] & 31u;
-        key_set(w, j, code);
-        solved &= code == (u32)(u8)kTables.solved[j];
-    }
-    const uint4 key = make_uint4(w[0], w[1], w[2], w[3]);
+    const uint4 key = key_from_column(roots, stride, col);
+    const bool solved = key_is_solved(key);
     const size_t base = (size_t)t * (m.capacity + 1);
     reinterpret_cast<uint4 *>(m.keys)[base + 1] = key;
     m.hash[(size_t)t * m.hash_size + (key_hash(key) & (m.hash_size - 1))] = 1;
@@ -159,42 +151,20 @@ __device__ __forceinline__ void expand_leaf_wave(const rc_mcts_t &m, u32 t, u32 
     const u32 a = lane & (kActionPad - 1);
 
     // child k = action k on the leaf (agents.py:512-513)
-    u32 w[4] = {0, 0, 0, 0};
-    bool solved = act;
-#pragma unroll
-    for (int j = 0; j < kPlanes; ++j) {
-        const u32 code = lut[a * (2 * kCodePad) + (j >= kCorners ? kCodePad : 0) + key_code(pk, j)];
-        key_set(w, j, code);
-        solved &= code == (u32)(u8)kTables.solved[j];
-    }
-    const uint4 ck = make_uint4(w[0], w[1], w[2], w[3]);
+    const uint4 ck = key_turned(pk, a, lut);
+    const bool solved = act && key_is_solved(ck);
 
     // membership in this tree (agents.py:517-520): linear probing, full-key compare
-    u32 h = key_hash(ck) & mask;
-    int found = 0;
-    if (act) {
-        for (;;) {
-            const int s = tab[h];
-            if (s == 0) break;
-            if (key_eq(keys[s], ck)) { found = s; break; }
-            h = (h + 1) & mask;
-        }
-    }
+    u32 h = 0;
+    const int found = act ? key_find(tab, mask, keys, ck, h) : 0;
     // unseen children take the next indices in child order (agents.py:523)
     const u64 newm = __ballot(act && found == 0);
     const int rank = __popcll(newm & ((1ull << lane) - 1ull));
     const int idx = found ? found : n + 1 + rank;
     // network input: the new children, packed in child order at columns 11 slot + rank (a non-root leaf has at most 11: its
     // parent is known); the root's step evaluates the root itself first, then children 0..9
-    if (act && !found && rank < (root ? 10 : 11)) {
-        const size_t col = col0 + (u32)rank + (root ? 1u : 0u);
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j) m.child_soa[(size_t)j * m.child_stride + col] = (int8_t)key_code(ck, j);
-    }
-    if (root && lane == kA) {
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j) m.child_soa[(size_t)j * m.child_stride + col0] = (int8_t)key_code(pk, j);
-    }
+    if (act && !found && rank < (root ? 10 : 11)) key_to_column(ck, m.child_soa, m.child_stride, col0 + (u32)rank + (root ? 1u : 0u));
+    if (root && lane == kA) key_to_column(pk, m.child_soa, m.child_stride, col0);
     if (act && !found) {
         keys[idx] = ck;
         for (;;) {   // claim the first free slot from where the lookup stopped (siblings race here)
@@ -242,11 +212,7 @@ __device__ __forceinline__ void expand_leaf_wave(const rc_mcts_t &m, u32 t, u32 
 __device__ __forceinline__ void expand_root_b(const rc_mcts_t &m, u32 t, u32 slot, u32 lane) {
     const uint4 *keys = reinterpret_cast<const uint4 *>(m.keys) + (size_t)t * (m.capacity + 1);
     const size_t col0 = (size_t)m.rows_per_tree * slot;
-    if (lane < 2) {
-        const uint4 ck = keys[2 + 10 + lane];
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j) m.child_soa[(size_t)j * m.child_stride + col0 + lane] = (int8_t)key_code(ck, j);
-    }
+    if (lane < 2) key_to_column(keys[2 + 10 + lane], m.child_soa, m.child_stride, col0 + lane);
     if (lane == 0) m.expanded[t] = 1;
 }
 
@@ -1346,12 +1312,7 @@ __global__ __launch_bounds__(kBlock) void k_mcts_complete_graph(rc_mcts_t m) {
     for (u32 w = blockIdx.y * kBlock + threadIdx.x; w < n * kA; w += kBlock * gridDim.y) {
         const u32 node = 1 + w / kA, a = w % kA;
         if (!m.leaf[base + node]) continue;
-        const uint4 pk = keys[node];
-        u32 kw[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < kPlanes; ++j)
-            key_set(kw, j, lut[a * (2 * kCodePad) + (j >= kCorners ? kCodePad : 0) + key_code(pk, j)]);
-        const uint4 ck = make_uint4(kw[0], kw[1], kw[2], kw[3]);
+        const uint4 ck = key_turned(keys[node], a, lut);
         u32 h = key_hash(ck) & mask;
         int found = 0;
         for (u32 probes = 0;; ++probes) {
@@ -1527,8 +1488,7 @@ __global__ __launch_bounds__(kBlock) void k_mcts_rehash(rc_mcts_t m, const rc_mc
     const u32 n = (u32)src.n_nodes[ts];
     if (n > m.capacity || n > src.capacity) return;   // (status written by k_mcts_copy_trees)
     int *tab = m.hash + (size_t)t * m.hash_size;
-    uint4 *tab4 = reinterpret_cast<uint4 *>(tab);
-    for (u32 i = threadIdx.x; i < m.hash_size / 4; i += kBlock) tab4[i] = make_uint4(0, 0, 0, 0);
+    hash_row_clear(tab, m.hash_size);
     __syncthreads();
     const uint4 *keys = reinterpret_cast<const uint4 *>(m.keys) + (size_t)t * (m.capacity + 1);
     const u32 mask = m.hash_size - 1;

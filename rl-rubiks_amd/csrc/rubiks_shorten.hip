@@ -12,7 +12,7 @@
 
 #include <algorithm>
 
-#include "rubiks_common.h"
+#include "rubiks_keys.h"
 
 namespace rubiks {
 
@@ -46,13 +46,6 @@ __device__ __forceinline__ bool load_game(const rc_shorten_t &s, u32 g, Game &q)
 // game blockIdx.x if it is still RC_SHORTEN_OK (the kernels after the replay)
 __device__ __forceinline__ bool game_ok(const rc_shorten_t &s, u32 g, Game &q) {
     return s.status[g] == RC_SHORTEN_OK && load_game(s, g, q);
-}
-
-__device__ __forceinline__ uint4 turned(const uint4 &pk, u32 a, const u8 *lut) {
-    u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < kPlanes; ++j) key_set(w, j, lut[a * (2 * kCodePad) + (j >= kCorners ? kCodePad : 0) + key_code(pk, j)]);
-    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // ---- status of every game, then s_0 .. s_L of the selected ones: three games per wave, one lane per cubie -------------------
@@ -206,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void k_shorten_neighbours(rc_shorten_t s) {
     for (unsigned long long w = (unsigned long long)blockIdx.y * kBlock + threadIdx.x; w < work; w += (unsigned long long)kBlock * gridDim.y) {
         const u32 p = (u32)(w / kA), a = (u32)(w % kA);
         if (ids[p] != (int)p + 1) continue;   // a state that was here before: its node is the earlier position
-        const int found = find_node(tab, keys, ids, q, turned(keys[p], a, lut));
+        const int found = find_node(tab, keys, ids, q, key_turned(keys[p], a, lut));
         if (found < 0) {
             s.status[g] = RC_SHORTEN_FAILED;
             continue;

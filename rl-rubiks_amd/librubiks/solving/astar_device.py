@@ -17,7 +17,7 @@ import torch
 from librubiks import _hip
 from librubiks.cube.device import DeviceCubes, encode
 from librubiks.model import make_inference_net, net_fingerprint
-from librubiks.solving.mcts_device import unpack_keys
+from librubiks.solving.keys import unpack_keys
 from librubiks.solving.results import QueueTable
 
 RUNNING, SOLVED, EXHAUSTED, OPEN_EMPTY, ROOT_SOLVED = 0, 1, 2, 3, 4

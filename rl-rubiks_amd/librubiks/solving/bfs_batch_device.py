@@ -17,6 +17,7 @@ import torch
 
 from librubiks import _hip
 from librubiks.cube.device import DeviceCubes
+from librubiks.solving.keys import unpack_keys
 from librubiks.solving.lockstep_device import pinned_copy, take_queue_rows
 
 RUNNING, SOLVED, CUT, FAILED, ROOT_SOLVED, GRAPH_DONE, EMPTY = 0, 1, 2, 3, 4, 5, 6
@@ -145,7 +146,6 @@ class BFSBatch:
 
     def node_arrays(self, slot: int, n: int) -> dict:
         """Host copies of the first n node rows of `slot` (for tests)."""
-        from librubiks.solving.mcts_device import unpack_keys
         return {"states": unpack_keys(self.keys[slot, :n].cpu().numpy().view(np.uint32)),
                 "parent": self.parent[slot, :n].cpu().numpy(), "action": self.action[slot, :n].cpu().numpy()}
 

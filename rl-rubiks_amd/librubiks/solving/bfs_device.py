@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from librubiks import _hip
+from librubiks.solving.keys import unpack_keys
 
 N_ACT = 12
 NONE = 2 ** 64 - 1
@@ -130,7 +131,6 @@ class BFSDevice:
 
     def node_arrays(self, n: int = None) -> dict:
         """Host copies of the first n committed nodes (for tests)."""
-        from librubiks.solving.mcts_device import unpack_keys
         n = self.committed if n is None else n
         return {"states": unpack_keys(self.keys[:n].cpu().numpy().view(np.uint32)),
                 "parent": self.parent[:n].cpu().numpy(), "action": self.action[:n].cpu().numpy()}

@@ -22,6 +22,7 @@ from librubiks import _hip
 from librubiks._vmm import VmmArray, zeros_or_trim
 from librubiks.cube.device import DeviceCubes, encode
 from librubiks.model import make_inference_net, net_fingerprint
+from librubiks.solving.keys import unpack_keys
 
 RUNNING, SOLVED, EXHAUSTED, PATH_OVERFLOW, ROOT_SOLVED, CORRUPT = 0, 1, 2, 3, 4, 5
 N_ACT = 12
@@ -67,15 +68,6 @@ _hip.register({
     "rc_mcts_shorten": [POINTER(_McStruct), c_void_p],
     "rc_mcts_copy_trees": [POINTER(_McStruct), POINTER(_McStruct), c_void_p, c_uint32, c_uint32, c_void_p],
 }, restypes={"rc_mcts_struct_bytes": ctypes.c_size_t})
-
-
-def unpack_keys(keys: np.ndarray) -> np.ndarray:
-    """(n,4) uint32 packed states -> (n,20) int8 codes (6 codes of 5 bits per dword)."""
-    keys = keys.astype(np.uint32).reshape(-1, 4)
-    out = np.empty((len(keys), 20), dtype=np.int8)
-    for j in range(20):
-        out[:, j] = (keys[:, j // 6] >> np.uint32(5 * (j % 6))) & np.uint32(31)
-    return out
 
 
 _PER_NODE = ("keys", "node", "V", "leaf")

@@ -8,7 +8,7 @@ It restates the reference's semantics (oracle/agents.py, class AStar) and the co
 kernels' code: a dict from state.tobytes() to index per problem, heapq on (cost, index) for the open list, first occurrence in row
 order, oracle.cube.expand12 for the children, the two fancy assignments of AStar._relax_seen literally -- so gather-before-scatter
 and last-write-wins are NumPy's own -- and cost = lambda * G - value in float64 from the float32 value, product and sum rounded
-separately.  key_hash and the 5-bit packing of csrc/rubiks_common.h are restated in uint32 arithmetic for two things only: to write
+separately.  key_hash and the 5-bit packing (tests/keys_model.py) are used for two things only: to write
 `keys` / `child_keys`, and to classify hashing events for the counters.
 
 What `differences` compares, after every launch:
@@ -36,6 +36,7 @@ import heapq
 
 import numpy as np
 
+from keys_model import home_cell, pack_keys
 from lockstep_model import FILL, N_ACT, filled, near_roots, replant_list
 from oracle import agents as oa
 from oracle import cube as oc
@@ -52,32 +53,6 @@ FILL_I8 = FILL - 256
 def min_hash_size(C: int) -> int:
     """The smallest hash row check_astar admits: a power of two >= 2 (C + 1)."""
     return 1 << int(2 * (C + 1) - 1).bit_length()
-
-
-def pack_keys(states: np.ndarray) -> np.ndarray:
-    """[n, 20] codes -> uint32 [n, 4]: 5 bits a code, six codes a word (cubies 0-5, 6-11, 12-17, 18-19)."""
-    codes = states.astype(np.int64).astype(np.uint32) & np.uint32(31)
-    w = np.zeros((len(states), 4), dtype=np.uint32)
-    for j in range(20):
-        w[:, j // 6] |= codes[:, j] << np.uint32(5 * (j % 6))
-    return w
-
-
-def key_hash(w: np.ndarray) -> np.ndarray:
-    """key_hash of csrc/rubiks_common.h on uint32 [n, 4], modulo 2^32."""
-    w = w.astype(np.uint32)
-    with np.errstate(over="ignore"):
-        h = w[:, 0] * np.uint32(0x9E3779B1)
-        h ^= h >> np.uint32(15)
-        h += w[:, 1] * np.uint32(0x85EBCA77)
-        h ^= h >> np.uint32(13)
-        h += w[:, 2] * np.uint32(0xC2B2AE3D)
-        h ^= h >> np.uint32(16)
-        h += w[:, 3] * np.uint32(0x27D4EB2F)
-        h ^= h >> np.uint32(15)
-        h *= np.uint32(0x165667B1)
-        h ^= h >> np.uint32(16)
-    return h
 
 
 class AStarModel:
@@ -122,7 +97,7 @@ class AStarModel:
         self.states[b, 1] = state
         self.keys[b, 1] = pack_keys(state[None])[0]
         self.taken[b] = False
-        self.taken[b, int(key_hash(self.keys[b, 1:2])[0]) & (self.H - 1)] = True
+        self.taken[b, home_cell(self.keys[b, 1:2], self.H)[0]] = True
         self.G[b, 1] = self.parents[b, 1] = self.parent_actions[b, 1] = 0
         self.index[b] = {} if solved else {state.tobytes(): 1}   # the reference returns before it inserts a solved root
         self.heap[b] = [] if solved else [(0.0, 1)]
@@ -213,7 +188,7 @@ class AStarModel:
             c["seen_node_reached_by_two_rows"] += int((seen & ~first).sum())
             # hashing: where the read-only probe of a new state stops in the row as it was before the launch
             mask = self.H - 1
-            homes = (key_hash(packed[first_unseen]) & np.uint32(mask)).astype(int).tolist()
+            homes = home_cell(packed[first_unseen], self.H).tolist()
             stops = [self._probe(b, h) for h in homes]
             c["two_new_states_one_probe_stop"] += len(stops) - len(set(stops))
             c["probe_wrapped"] += sum(s < h for s, h in zip(stops, homes))
@@ -366,7 +341,7 @@ class AStarModel:
             and len(np.unique(pb * (C + 2) + node)) == len(node)
         if ok and len(node):
             mask = H - 1
-            home = (key_hash(self.keys[pb, node]) & np.uint32(mask)).astype(np.int64)
+            home = home_cell(self.keys[pb, node], H)
             dist = (slot - home) & mask
             for k in range(int(dist.max())):
                 far = dist > k

@@ -7,7 +7,7 @@ the kernels with it after every call).
 It restates the reference's FIFO loop (oracle/agents.py, class BFS) and the comments of include/rubiks_hip.h, and nothing of the
 kernels' code: per slot a dict from state.tobytes() to node index, oracle.cube.expand12 for the twelve children of a chunk's
 parents, first occurrence in row order for new states, and the cut test "stored states >= max_states before a parent's pop".
-key_hash (tests/mcts_lockstep.py) and the 5-bit packing (tests/astar_model.py) are used for two things only: to write `keys` /
+key_hash and the 5-bit packing (tests/keys_model.py) are used for two things only: to write `keys` /
 `child_keys`, and to classify hashing events for the counters.
 
 What `differences` compares, after every call:
@@ -34,9 +34,9 @@ import functools
 
 import numpy as np
 
-from astar_model import U32_MAX, after, pack_keys
+from astar_model import U32_MAX, after
+from keys_model import check_hash_table, home_cell, pack_keys
 from lockstep_model import FILL, N_ACT, Arena, filled, near_roots, replant_list
-from mcts_lockstep import check_hash_table, key_hash
 from oracle import cube as oc
 
 RUNNING, SOLVED, CUT, FAILED, ROOT_SOLVED, GRAPH_DONE, EMPTY = range(7)
@@ -115,7 +115,7 @@ class BfsBatchModel:
                 self.count["root_solved"] += 1
                 continue
             self.index[s], self.committed[s], self.hash_state[s] = {state.tobytes(): 0}, 1, "table"
-            self.taken[s, int(key_hash(self.keys[s, :1])[0]) & (self.H - 1)] = True
+            self.taken[s, home_cell(self.keys[s, :1], self.H)[0]] = True
             w[W_STATUS, s], w[W_NODES, s], w[W_LEVELS, s], w[W_LEVEL_END, s] = RUNNING, 1, 1, 1
             self._next_chunk(s)
 
@@ -202,7 +202,7 @@ class BfsBatchModel:
                 c["duplicate_across_workgroups"] += int((row0 + r) // 256 != (row0 + first_row[k]) // 256)
         mask = self.H - 1
         new_rows = np.flatnonzero(new)
-        homes = (key_hash(packed[new_rows]) & mask).astype(int).tolist()
+        homes = home_cell(packed[new_rows], self.H).tolist()
         c["two_new_states_one_home_cell"] += len(homes) - len(set(homes))
         taken = self.taken[s].copy()   # the cells the new states claim, whether or not the step commits them
         for h in homes:
@@ -342,7 +342,7 @@ class BfsBatchModel:
         # a positive cell may sit behind pending cells, and a pending cell behind either: no empty cell on the way
         cells = np.flatnonzero(row)
         key_of = np.array([self.keys[s, row[x] - 1] if row[x] > 0 else self.child_keys[s * self.seg - row[x] - 1] for x in cells], dtype=np.uint32)
-        home = (key_hash(key_of.reshape(-1, 4)) & mask).astype(np.int64)
+        home = home_cell(key_of.reshape(-1, 4), self.H)
         for x, h in zip(cells.tolist(), home.tolist()):
             if any(row[(h + j) & mask] == 0 for j in range((x - h) & mask)):
                 return False

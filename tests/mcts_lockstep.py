@@ -8,9 +8,10 @@ import ctypes
 import numpy as np
 import torch
 
+from keys_model import check_hash_table  # noqa: F401  (the MCTS tests take it from here)
+
 TREE_KEYS = ("states", "neighbors", "leaves", "N", "L", "V", "W", "P")
 WRAP = 65536 - 48      # iteration number planted by `drive(what="wrap")`: 48 iterations before the 16-bit path number wraps
-_M32 = 0xFFFFFFFF
 
 
 def compare_tree(tree: dict, ref: dict, n: int):
@@ -33,38 +34,6 @@ def oracle_arrays(ref) -> dict:
 def standin_from_golden(npz):
     from standin_net import StandInNet
     return StandInNet(weights={k[4:]: npz[k] for k in npz.files if k.startswith("net_") and not k.startswith("net_probe")})
-
-
-def key_hash(keys: np.ndarray) -> np.ndarray:
-    """csrc/rubiks_common.h key_hash of packed keys ([n, 4] uint32), vectorised."""
-    k = keys.astype(np.uint64)
-    h = (k[:, 0] * 0x9E3779B1) & _M32
-    h ^= h >> 15
-    h = (h + k[:, 1] * 0x85EBCA77) & _M32
-    h ^= h >> 13
-    h = (h + k[:, 2] * 0xC2B2AE3D) & _M32
-    h ^= h >> 16
-    h = (h + k[:, 3] * 0x27D4EB2F) & _M32
-    h ^= h >> 15
-    h = (h * 0x165667B1) & _M32
-    h ^= h >> 16
-    return h
-
-
-def check_hash_table(table: np.ndarray, keys: np.ndarray, n: int):
-    """The linear-probing table of a tree of n nodes (keys: its rows 0 .. n, packed): every filled slot names a node 1 .. n, each node
-    exactly once, and each node sits on the probe from key_hash(key) & mask with no empty slot before it."""
-    size = len(table)
-    mask = size - 1
-    filled = np.flatnonzero(table)
-    assert np.array_equal(np.sort(table[filled]), np.arange(1, n + 1))
-    where = np.empty(n + 1, dtype=np.int64)
-    where[table[filled]] = filled
-    home = key_hash(keys[1:n + 1].view(np.uint32).reshape(-1, 4)) & mask
-    for i in range(1, n + 1):
-        h, s = int(home[i - 1]), int(where[i])
-        steps = (s - h) & mask
-        assert all(table[(h + j) & mask] != 0 for j in range(steps)), f"node {i}: an empty slot on its probe"
 
 
 def _scramble_rings(f, rng, seq_sel: np.ndarray):

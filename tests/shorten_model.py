@@ -6,6 +6,7 @@ order of the inserts and is not modelled: tables are compared through look-ups).
 """
 import numpy as np
 
+from keys_model import home_cell, pack_keys
 from oracle import cube
 
 OK, SKIPPED, BAD_ACTION, FAILED, NO_ROOM = 0, 1, 2, 3, 4
@@ -15,33 +16,10 @@ BLOCK = 256      # threads of the search's workgroup: a level's scan items are c
 N_ACT = 12
 
 
-def pack(state: np.ndarray) -> tuple:
-    """20 codes of 5 bits, 6 per 32-bit word (cubies 0-5, 6-11, 12-17, 18-19)."""
-    w = [0, 0, 0, 0]
-    for j, c in enumerate(np.asarray(state, dtype=np.int64)):
-        w[j // 6] |= (int(c) & 31) << (5 * (j % 6))
-    return tuple(w)
-
-
-def key_hash(k) -> int:
-    """The kernels' hash of a packed key (csrc/rubiks_common.h): the home cell is key_hash & (cells - 1)."""
-    M = 0xFFFFFFFF
-    h = (int(k[0]) * 0x9E3779B1) & M
-    h ^= h >> 15
-    h = (h + int(k[1]) * 0x85EBCA77) & M
-    h ^= h >> 13
-    h = (h + int(k[2]) * 0xC2B2AE3D) & M
-    h ^= h >> 16
-    h = (h + int(k[3]) * 0x27D4EB2F) & M
-    h ^= h >> 15
-    h = (h * 0x165667B1) & M
-    return h ^ (h >> 16)
-
-
 def lookup(cells: np.ndarray, keys: np.ndarray, key) -> int:
     """What a probe of a game's table (its `cells`, its rows of `keys`) finds for `key`: the node, 0 if there is none."""
     mask = len(cells) - 1
-    h = key_hash(key) & mask
+    h = int(home_cell(np.asarray(key, dtype=np.uint32)[None], len(cells))[0])
     for _ in range(len(cells)):
         c = int(cells[h])
         if c == 0:
@@ -92,7 +70,7 @@ class Batch:
         self.keys, self.ids, self.nbr, self.claim = f((P, 4), np.uint32), f((P,), np.int32), f((P, 12), np.int32), f((P, 2), np.int32)
         self.frontier_a, self.frontier_b = f((P,), np.int32), f((P,), np.int32)
         self.out_queues, self.out_lens, self.status = f((G, self.out_width), np.uint8), f((G,), np.int32), f((G,), np.int32)
-        self.tables = [dict() for _ in range(G)]     # packed key -> node
+        self.tables = [dict() for _ in range(G)]     # packed key (its bytes) -> node
         self.states = [None] * G                     # (L + 1, 20) of the games that were replayed
         self.counts = [dict() for _ in range(G)]
 
@@ -142,9 +120,9 @@ def index(b: Batch):
             states[i + 1] = cube.rotate(states[i], *cube.ACTION_SPACE[int(a)])
         b.states[g] = states
         table = b.tables[g] = {}
+        b.keys[p0:p0 + L + 1] = pack_keys(states)
         for p in range(L + 1):
-            k = pack(states[p])
-            b.keys[p0 + p] = k
+            k = b.keys[p0 + p].tobytes()
             if k in table:
                 _bump(c, "revisits")
             else:
@@ -162,9 +140,9 @@ def neighbours(b: Batch):
         for p in range(L + 1):
             if b.ids[p0 + p] != p + 1:
                 continue
-            kids = cube.expand12(b.states[g][p][None])
+            kids = pack_keys(cube.expand12(b.states[g][p][None]))
             for a in range(N_ACT):
-                v = table.get(pack(kids[a]), 0)
+                v = table.get(kids[a].tobytes(), 0)
                 b.nbr[p0 + p, a] = v
                 _bump(c, "edges" if v else "no_edge")
 

@@ -4,7 +4,7 @@ prefix sum, gather, the stand-in network on the gathered states, push -- its pro
 by problem: every state, G, parent and parent action, the sorted open list, the node count, the solved flag, the action queue and
 the status.  That is what makes it a reference for tests/test_astar_kernels_gpu.py rather than a copy of the kernels.  Also here,
 because it needs no GPU: the scenarios of that module reach every branch they are meant to reach (seeds and scripts are chosen
-here), and the restated packing and hash function are checked against values worked out by hand.
+here).  The packing and the hash function it uses are pinned in tests/test_keys_model.py.
 """
 import numpy as np
 import pytest
@@ -61,26 +61,6 @@ def test_the_model_plays_the_oracles_games(onet, lam, N, max_states):
         seen.add(want)
     assert seen == {am.ROOT_SOLVED, am.SOLVED, am.EXHAUSTED}
     assert (m.claim == am.INT_MAX).all()
-
-
-def test_packing_and_hash_are_the_headers():
-    """Six 5-bit codes a word, and key_hash of csrc/rubiks_common.h worked out step by step in Python integers."""
-    state = np.arange(20, dtype=np.int8) + 3
-    w = am.pack_keys(state[None])[0].tolist()
-    assert w == [sum(int(state[6 * k + j]) << (5 * j) for j in range(6) if 6 * k + j < 20) for k in range(4)]
-    M = (1 << 32) - 1
-    h = (w[0] * 0x9E3779B1) & M
-    h ^= h >> 15
-    h = (h + w[1] * 0x85EBCA77) & M
-    h ^= h >> 13
-    h = (h + w[2] * 0xC2B2AE3D) & M
-    h ^= h >> 16
-    h = (h + w[3] * 0x27D4EB2F) & M
-    h ^= h >> 15
-    h = (h * 0x165667B1) & M
-    h ^= h >> 16
-    assert int(am.key_hash(np.array([w], dtype=np.uint32))[0]) == h
-    assert [am.min_hash_size(C) for C in (13, 63, 255, 1023, 2047, 31, 64)] == [32, 128, 512, 2048, 4096, 64, 256]
 
 
 def test_the_cost_is_rounded_twice():

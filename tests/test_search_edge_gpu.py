@@ -26,32 +26,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import agents as oa  # noqa: E402  (checker only)
 from oracle import cube as oc  # noqa: E402
-
-_M32 = 0xFFFFFFFF
-
-
-def _pack_key(state: np.ndarray) -> np.ndarray:
-    """int8[20] -> uint32[4]: 20 codes of 5 bits, 6 per dword (csrc/rubiks_common.h key_set)."""
-    k = [0, 0, 0, 0]
-    for j, code in enumerate(state):
-        k[j // 6] |= (int(code) & 31) << (5 * (j % 6))
-    return np.array(k, dtype=np.uint32)
-
-
-def _key_hash(k) -> int:
-    """csrc/rubiks_common.h key_hash."""
-    h = (int(k[0]) * 0x9E3779B1) & _M32
-    h ^= h >> 15
-    h = (h + int(k[1]) * 0x85EBCA77) & _M32
-    h ^= h >> 13
-    h = (h + int(k[2]) * 0xC2B2AE3D) & _M32
-    h ^= h >> 16
-    h = (h + int(k[3]) * 0x27D4EB2F) & _M32
-    h ^= h >> 15
-    h = (h * 0x165667B1) & _M32
-    h ^= h >> 16
-    return h
-
+from keys_model import home_cell, pack_keys  # noqa: E402
 
 def _compare(tree: dict, ref, n: int):
     assert tree["n"] == n == len(ref)
@@ -110,8 +85,8 @@ def test_leaf_with_all_children_known(net_gpu):
             idx = n + 1 + i
             ref.indices[kids[k].tobytes()] = idx
             ref.states[idx], ref.P[idx], ref.V[idx], ref.W[idx] = kids[k], p[i], v[i], v[i]
-            key = _pack_key(kids[k])
-            slot = _key_hash(key) & (forest.hash_size - 1)
+            key = pack_keys(kids[k][None])[0]
+            slot = int(home_cell(key[None], forest.hash_size)[0])
             while table[slot] != 0:
                 slot = (slot + 1) & (forest.hash_size - 1)
             table[slot] = idx
