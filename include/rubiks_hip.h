@@ -989,6 +989,111 @@ int rc_shorten_bfs(const rc_shorten_t *s, rc_stream_t stream);
 /* rc_shorten_index, rc_shorten_neighbours, rc_shorten_bfs on `stream`. */
 int rc_shorten(const rc_shorten_t *s, rc_stream_t stream);
 
+/* ---- the near-solved table: exact distances, optimal tails, tighter queues (csrc/rubiks_near.hip) ---------------------
+ *
+ * Every state within K quarter turns of the solved cube, found by the breadth-first search of librubiks/solving/agents.py:92-131
+ * (class BFS) started at the SOLVED state, with rc_bfs_*'s numbering: nodes in discovery order (node 0 = solved, depth 0), the
+ * frontier of a level a contiguous node range, child row 12 p + k = action k on the p-th parent of a chunk, a row new iff its
+ * state is neither stored nor produced by a lower row of the chunk, new rows appended in row order.  There is no target and no
+ * max_states, and the solved state is stored.  A level is expanded in chunks of at most chunk_rows / 12 parents; the table does
+ * not depend on the chunking.  Per node: the packed key (20 codes of 5 bits, 6 per word, as rc_bfs) and one meta byte
+ * depth << 4 | action, the action being the k of the row that created the node (0 for the root).  Cells: open addressing, linear
+ * probing from key_hash & (hash_size - 1); 0 = free, c > 0 = node c - 1, c < 0 = pending row -(c + 1) while a chunk is filled.
+ *
+ * With a_1 .. a_d the actions along the discoverers from solved to a state, solved turned by a_1, .., a_d IS the state, d is
+ * its exact distance, and rev(a_d), .., rev(a_1) (rev(a) = a ^ 1) is an optimal solution.  States correspond one to one to
+ * group elements, so two action sequences with the same product on solved have the same effect on every state: a stretch of a
+ * queue whose product lies in the table may be replaced by that product's a_1 .. a_d (tightening), from any root.
+ *
+ * Node ids and cells are int32 and a depth is 4 bits; K <= RC_NEAR_MAX_DEPTH = 8 (86 049 153 nodes, 2^28 cells: about 2.5 GB).
+ * Device pointers throughout; words, and the build arrays, are only needed by rc_near_begin / rc_near_expand. */
+#define RC_NEAR_MAX_DEPTH 8
+#define RC_NEAR_OK 0
+#define RC_NEAR_CORRUPT 1        /* a cell, meta byte or walk back did not name what the build writes: the lane's result is -1 */
+
+typedef struct rc_near {
+    uint32_t depth;       /* K, 1 .. RC_NEAR_MAX_DEPTH */
+    uint32_t capacity;    /* node rows, < 2^30 */
+    uint32_t hash_size;   /* cells: a power of two >= 2 * capacity, <= 2^30 */
+    uint32_t n_nodes;     /* nodes a lookup may meet (the host's word after the build; 0 while building) */
+    uint32_t chunk_rows;  /* build: rows of the child arrays, >= 12 */
+    uint32_t reserved;
+    void *keys;           /* [capacity] uint32[4], 16-byte aligned */
+    uint8_t *meta;        /* [capacity] depth << 4 | action */
+    int32_t *hash;        /* [hash_size] */
+    uint32_t *words;      /* build, [4]: nodes stored, 1 = a new state found no node row, new rows of the last chunk, 0 */
+    void *child_keys;     /* build, [chunk_rows] uint32[4] */
+    int32_t *child_slot;  /* build, [chunk_rows] */
+    uint32_t *flags;      /* build, [chunk_rows] 1 = new state */
+    uint32_t *prefix;     /* build, [chunk_rows] exclusive prefix sum of flags */
+    void *scan_tmp;       /* build, rc_near_scan_bytes(chunk_rows) bytes */
+    size_t scan_tmp_bytes;
+} rc_near_t;
+
+size_t rc_near_struct_bytes(void);
+size_t rc_near_scan_bytes(uint32_t chunk_rows);
+/* agents.py:92-103 with the solved state as the root: clears the cells, stores node 0, words = {1, 0, 0}. */
+int rc_near_begin(const rc_near_t *t, rc_stream_t stream);
+/* agents.py:104-129 for parents lo .. lo + n_parents - 1 (12 n_parents <= chunk_rows) of level `level` - 1: children, lookup
+ * against the cells, claims (the lowest row of a state wins), flags, scan, append with meta level << 4 | k, words[0] += new rows.
+ * Nothing is read back: the host reads words once a level is done (its count decides whether another level starts).  A new
+ * state beyond `capacity` is not stored and sets words[1]. */
+int rc_near_expand(const rc_near_t *t, uint32_t lo, uint32_t n_parents, uint32_t level, rc_stream_t stream);
+/* One lane per state of soa ([20][stride] code planes, state i in column i): depth_out[i] = its depth, -1 if it is farther
+ * than K; node_out (may be NULL) its node or -1.  *status (int32, set to RC_NEAR_OK by the caller) becomes RC_NEAR_CORRUPT if a
+ * probe met a cell or meta byte the build does not write; probes are bounded by hash_size. */
+int rc_near_depth(const rc_near_t *t, const int8_t *soa, size_t n, size_t stride, int8_t *depth_out, int32_t *node_out, int32_t *status,
+                  rc_stream_t stream);
+/* One lane per state: out_lens[i] = its depth d or -1, and for d > 0 row i of out_queues ([n][out_width], out_width >= K) holds
+ * rev(a_d) .. rev(a_1), found by walking back d times: a = action(node), state <- state turned by rev(a), looked up at depth
+ * one less.  A state on the way that is not there at that depth: RC_NEAR_CORRUPT and length -1. */
+int rc_near_solve(const rc_near_t *t, const int8_t *soa, size_t n, size_t stride, uint8_t *out_queues, uint32_t out_width, int32_t *out_lens,
+                  int32_t *status, rc_stream_t stream);
+
+/* Tightening a batch of action queues (rows, lengths and a select mask as rc_shorten_t; no roots).  For game g with queue q of L
+ * moves and W = min(L, window): d(i, j) = depth of solved turned by q[i] .. q[j - 1] for i < j <= min(L, i + W), or none; byte
+ * band[band_off[g] + i W + (j - i - 1)] holds it (255 = none).  best[0] = 0, best[j] = min over max(0, j - W) <= i < j with d(i, j)
+ * defined of best[i] + d(i, j), a tie going to the smallest i (from[j]); d(j - 1, j) = 1 always.  The chosen i are followed back
+ * from L and every chosen segment writes a_1 .. a_d of its product at out_queues[g][best[i] ..]; the length best[L] <= L goes to
+ * out_lens[g].  Game g owns positions pos_off[g] .. (at least L + 1) of best / from and at least L W band bytes. */
+#define RC_NEAR_T_MAX_LEN ((1 << 27) - 2)
+#define RC_NEAR_T_OK 0          /* as RC_SHORTEN_*: so far every step has run */
+#define RC_NEAR_T_SKIPPED 1     /* select[g] == 0 */
+#define RC_NEAR_T_BAD_ACTION 2  /* a queue byte >= 12 inside the game's length: found before it indexes anything */
+#define RC_NEAR_T_FAILED 3      /* a length, offset, cell or word read from memory does not name this game's or the table's data */
+#define RC_NEAR_T_NO_ROOM 4     /* best[L] > out_width: out_lens[g] holds it, no byte of the row is written */
+
+typedef struct rc_near_tighten {
+    uint32_t n_games;         /* G >= 1 */
+    uint32_t queue_width;     /* bytes per row of `queues` */
+    uint32_t out_width;       /* bytes per row of `out_queues` */
+    uint32_t max_len;         /* the host's word: no selected game has lens[g] above it; <= min(queue_width, RC_NEAR_T_MAX_LEN) */
+    uint32_t window;          /* >= 1; the whole queue: any value >= max_len */
+    uint32_t reserved;
+    size_t total_positions;   /* P = pos_off[G] >= 1 */
+    size_t total_band;        /* band_off[G] */
+    const uint8_t *queues;    /* [G][queue_width] */
+    const int32_t *lens;      /* [G] */
+    const uint8_t *select;    /* [G] 0: leave the game alone */
+    const uint64_t *band_off; /* [G + 1] prefix sums made on the host */
+    const uint64_t *pos_off;  /* [G + 1] */
+    uint8_t *band;            /* [total_band] */
+    int32_t *best;            /* [P] */
+    int32_t *from;            /* [P] the chosen i; ~i once the walk back has chosen the segment */
+    uint8_t *out_queues;      /* [G][out_width] */
+    int32_t *out_lens;        /* [G] -1 where there is no result */
+    int32_t *status;          /* [G] RC_NEAR_T_* */
+} rc_near_tighten_t;
+
+size_t rc_near_tighten_struct_bytes(void);
+/* status and out_lens of ALL games (one wave per game reads its bytes), then the band of the games that are OK: one lane per
+ * start i carries the product move by move and probes the table at every step, two starts per lane in flight. */
+int rc_near_tighten_distances(const rc_near_t *t, const rc_near_tighten_t *s, rc_stream_t stream);
+/* The dynamic programme above, one wave per OK game reducing over i, then the walk back and the segments' sequences. */
+int rc_near_tighten_route(const rc_near_t *t, const rc_near_tighten_t *s, rc_stream_t stream);
+/* rc_near_tighten_distances, rc_near_tighten_route on `stream`. */
+int rc_near_tighten(const rc_near_t *t, const rc_near_tighten_t *s, rc_stream_t stream);
+
 /* ---- generalised move patterns in a batch of action sequences (csrc/rubiks_patterns.hip) ------------------------------
  *
  * The reference's find_generalized_patterns (librubiks/analysis/pattern_mining.py:8-45): over every contiguous sub-sequence of

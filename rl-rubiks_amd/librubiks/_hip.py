@@ -93,9 +93,22 @@ SIGNATURES = {
     "rc_patterns_extend": [P, P],
     "rc_patterns_close": [P, P],
     "rc_patterns_level": [P, P],
+    # the near-solved table (csrc/rubiks_near.hip); no search module imports librubiks/solving/near.py, so it is declared here.
+    # rc_near_t / rc_near_tighten_t go by address (ctypes.byref of near.py's mirrors)
+    "rc_near_struct_bytes": [],
+    "rc_near_tighten_struct_bytes": [],
+    "rc_near_scan_bytes": [ctypes.c_uint32],
+    "rc_near_begin": [P, P],
+    "rc_near_expand": [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, P],
+    "rc_near_depth": [P, P, SZ, SZ, P, P, P, P],
+    "rc_near_solve": [P, P, SZ, SZ, P, ctypes.c_uint32, P, P, P],
+    "rc_near_tighten_distances": [P, P, P],
+    "rc_near_tighten_route": [P, P, P],
+    "rc_near_tighten": [P, P, P],
 }
 _RESTYPES = {"rc_error_string": c_char_p, "rc_split_layer_struct_bytes": c_size_t, "rc_patterns_struct_bytes": c_size_t,
-             "rc_patterns_table_cells": c_size_t, "rc_patterns_workspace_bytes": c_size_t, "rc_patterns_hash": ctypes.c_uint64}
+             "rc_patterns_table_cells": c_size_t, "rc_patterns_workspace_bytes": c_size_t, "rc_patterns_hash": ctypes.c_uint64,
+             "rc_near_struct_bytes": c_size_t, "rc_near_tighten_struct_bytes": c_size_t, "rc_near_scan_bytes": c_size_t}
 
 _lib = None
 _initialised_devices = set()

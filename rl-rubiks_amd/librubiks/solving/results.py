@@ -88,6 +88,8 @@ class BatchResult:
         self.game_seconds = game_seconds
         # Set by `shortened` on the result it returns: the lengths the search itself found, and the wall seconds of the shortening.
         self.raw_lengths, self.shorten_seconds = None, None
+        # Set by `tightened` on the result it returns (which also sets raw_lengths where nothing has yet).
+        self.tighten_seconds = None
 
     def shortened(self, states, budget_bytes: int = None) -> "BatchResult":
         """
@@ -110,6 +112,30 @@ class BatchResult:
         lengths = np.where(solved, queues.lengths(), self.lengths).astype(np.asarray(self.lengths).dtype)
         out = BatchResult(self.solved, lengths, self.nodes, queues, self.seconds, self.iterations, self.status, self.game_seconds)
         out.raw_lengths, out.shorten_seconds = np.asarray(self.lengths).copy(), time.perf_counter() - t0
+        return out
+
+    def tightened(self, table, window: int = None, budget_bytes: int = None) -> "BatchResult":
+        """
+        The result with every SOLVED game's non-empty queue replaced by what `table` (a NearTable, librubiks/solving/near.py)
+        makes of it: every stretch of at most `window` moves (None: the whole queue) whose product lies within the table's depth
+        of solved gives way to that product's optimal sequence, chosen so that the queue is as short as such replacements can make
+        it.  Same product, hence still a solution; never longer.  Unsolved games keep their queues.  `raw_lengths` stays what an
+        earlier `shortened` recorded, else becomes this result's lengths, so `result.shortened(states).tightened(table)` still
+        tells what the search returned; `tighten_seconds` is the wall time this took; everything else is the search's.
+        """
+        import time
+
+        from librubiks.solving import near
+        t0 = time.perf_counter()
+        solved = np.asarray(self.solved, dtype=bool)
+        queues, status = table.tighten(self.queues, select=solved & (self.queues.lengths() > 0), window=window, budget_bytes=budget_bytes)
+        bad = np.flatnonzero((status != near.OK) & (status != near.SKIPPED))
+        if len(bad):
+            raise RuntimeError(f"tightening failed for games {bad[:8].tolist()}: {[near.STATUS_NAMES[int(s)] for s in status[bad[:8]]]}")
+        lengths = np.where(solved, queues.lengths(), self.lengths).astype(np.asarray(self.lengths).dtype)
+        out = BatchResult(self.solved, lengths, self.nodes, queues, self.seconds, self.iterations, self.status, self.game_seconds)
+        out.raw_lengths = np.asarray(self.lengths).copy() if self.raw_lengths is None else self.raw_lengths
+        out.shorten_seconds, out.tighten_seconds = self.shorten_seconds, time.perf_counter() - t0
         return out
 
     @property
