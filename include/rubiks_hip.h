@@ -1094,6 +1094,63 @@ int rc_near_tighten_route(const rc_near_t *t, const rc_near_tighten_t *s, rc_str
 /* rc_near_tighten_distances, rc_near_tighten_route on `stream`. */
 int rc_near_tighten(const rc_near_t *t, const rc_near_tighten_t *s, rc_stream_t stream);
 
+/* ---- beyond the table: exact distances and optimal solutions up to K + J quarter turns (csrc/rubiks_near_reach.hip) -----------
+ *
+ * The table is one half of a bidirectional search; this is the other.  For a state s and `extra` = J, levels j = 0, 1, .., J in
+ * turn: a sequence q of j actions (all 12^j of them, numbered as base-12 numbers with the first move most significant) is a HIT
+ * if s turned by q lies in the table, at depth d <= K.  The first level j* with a hit gives the exact distance D = j* + min d
+ * (a hit at level j with depth d means D <= j + d <= j + K, so the first level with a hit is max(0, D - K) and its smallest d is
+ * D - j*); no hit up to J: -1, "farther than K + J".  The solution is the hit with the smallest (d, index), followed by the
+ * optimal tail of the state it reaches exactly as rc_near_solve writes it; its length is D.
+ *
+ * Only CANONICAL sequences are walked, which changes no result, the tie included: (1) an action right after its inverse and
+ * (2) a third equal quarter turn in a row never occur in a hit at level j* (their product has a sequence two moves shorter,
+ * which would have hit two levels earlier); (3) an action on the higher-numbered of two opposite faces directly followed by one
+ * on the lower-numbered face has the same product as the two swapped, at a smaller index.
+ *
+ * Per state: best, a uint64 word that orders by (d, index): d << 40 | level << 36 | index (12^10 < 2^36), all ones = no hit yet;
+ * live, a byte that is 0 once the state has its distance from an EARLIER level.  A level is cut into work items: item w of
+ * level j is (state w / I, prefix w % I) with I = rc_near_reach_items(j, prefix) = 12^min(j, prefix); the lane of an item drops a
+ * prefix that is not canonical, else turns the state by it and walks the remaining j - min(j, prefix) moves depth-first, probing
+ * the leaves (the lower levels were hit-free) with two probes in flight, and merges its smallest hit into best by one 64-bit
+ * atomic minimum.  The host passes item ranges, so a launch is as long as the host lets it be; the results depend on neither
+ * the ranges nor `prefix`.  status: int32[2]; [0] is set to RC_NEAR_OK by the caller and becomes RC_NEAR_CORRUPT as for
+ * rc_near_depth (the lane's result is then no hit / -1); [1] is written by every begin / level call: the states that have no
+ * distance yet, which the host reads once a level is done to decide whether the next one runs. */
+#define RC_NEAR_REACH_MAX_EXTRA 10
+
+typedef struct rc_near_reach {
+    size_t n;             /* states, >= 1 */
+    size_t stride;        /* of soa */
+    uint32_t extra;       /* J, 0 .. RC_NEAR_REACH_MAX_EXTRA */
+    uint32_t prefix;      /* P, 0 .. RC_NEAR_REACH_MAX_EXTRA: moves of a sequence that the work-item number holds */
+    uint32_t out_width;   /* bytes per row of out_queues, >= K + J */
+    uint32_t reserved;
+    const int8_t *soa;    /* [20][stride] code planes, state i in column i */
+    uint8_t *live;        /* [n] */
+    uint64_t *best;       /* [n] */
+    int8_t *dist_out;     /* [n] finish: D or -1 */
+    int8_t *level_out;    /* [n] finish: j* or -1 */
+    uint8_t *out_queues;  /* [n][out_width] finish: the solution */
+    int32_t *out_lens;    /* [n] finish: D or -1 */
+    int32_t *status;      /* [2] see above */
+} rc_near_reach_t;
+
+size_t rc_near_reach_struct_bytes(void);
+/* Work items per state of level `level` with `prefix` = P: 12^min(level, P); 0 if either exceeds RC_NEAR_REACH_MAX_EXTRA. */
+uint64_t rc_near_reach_items(uint32_t level, uint32_t prefix);
+/* Level 0, which is rc_near_depth's probe: best[i] = d << 40 or all ones, live[i] = 1 where there is no hit; status[1]. */
+int rc_near_reach_begin(const rc_near_t *t, const rc_near_reach_t *r, rc_stream_t stream);
+/* Items first .. first + count - 1 (count >= 1, within n * rc_near_reach_items(level, prefix)) of level 1 <= `level` <= extra.
+ * First live[i] = (best[i] is all ones, or a word of this level) for every state, so the levels are to be called in turn and the
+ * ranges of one level in any order; then the items; then status[1].  Every loop of an item is bounded by its 12^(level - P)
+ * leaves and, within a probe, by the table's size as rc_near_depth's is. */
+int rc_near_reach_level(const rc_near_t *t, const rc_near_reach_t *r, uint32_t level, uint64_t first, uint64_t count, rc_stream_t stream);
+/* One lane per state: the winning word's index gives the first j* moves, rc_near_solve's walk back from the state they reach gives
+ * the rest (rev(a_d) .. rev(a_1)); dist_out, level_out, out_lens and the row are written.  A word that is not one a level writes,
+ * or a walk back that leaves the table: RC_NEAR_CORRUPT and -1.  out_width < K + J: RC_ERR_RANGE. */
+int rc_near_reach_finish(const rc_near_t *t, const rc_near_reach_t *r, rc_stream_t stream);
+
 /* ---- generalised move patterns in a batch of action sequences (csrc/rubiks_patterns.hip) ------------------------------
  *
  * The reference's find_generalized_patterns (librubiks/analysis/pattern_mining.py:8-45): over every contiguous sub-sequence of

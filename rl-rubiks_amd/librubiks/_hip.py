@@ -105,10 +105,17 @@ SIGNATURES = {
     "rc_near_tighten_distances": [P, P, P],
     "rc_near_tighten_route": [P, P, P],
     "rc_near_tighten": [P, P, P],
+    # ... and the search beyond it (csrc/rubiks_near_reach.hip); rc_near_reach_t by address as well
+    "rc_near_reach_struct_bytes": [],
+    "rc_near_reach_items": [ctypes.c_uint32, ctypes.c_uint32],
+    "rc_near_reach_begin": [P, P, P],
+    "rc_near_reach_level": [P, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, P],
+    "rc_near_reach_finish": [P, P, P],
 }
 _RESTYPES = {"rc_error_string": c_char_p, "rc_split_layer_struct_bytes": c_size_t, "rc_patterns_struct_bytes": c_size_t,
              "rc_patterns_table_cells": c_size_t, "rc_patterns_workspace_bytes": c_size_t, "rc_patterns_hash": ctypes.c_uint64,
-             "rc_near_struct_bytes": c_size_t, "rc_near_tighten_struct_bytes": c_size_t, "rc_near_scan_bytes": c_size_t}
+             "rc_near_struct_bytes": c_size_t, "rc_near_tighten_struct_bytes": c_size_t, "rc_near_scan_bytes": c_size_t,
+             "rc_near_reach_struct_bytes": c_size_t, "rc_near_reach_items": ctypes.c_uint64}
 
 _lib = None
 _initialised_devices = set()

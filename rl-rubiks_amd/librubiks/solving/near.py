@@ -9,9 +9,12 @@ queue's moves -- the queue with every stretch whose product lies in the table re
     table.depths(states)                    exact distances, -1 beyond K
     table.solve(states)                     optimal solutions of the states within K
     table.tighten(queues, ...)              tighter queues with the same product; plan_tighten_chunks is its pure planning step
+    table.reach(states, extra=J)            exact distances and optimal solutions up to K + J (csrc/rubiks_near_reach.hip)
     BatchResult.tightened(table)            the solved games of a search result (librubiks/solving/results.py)
+    BatchResult.excess(table, states, J)    how many moves each solution is longer than the optimum
 """
 import ctypes
+from collections import namedtuple
 from ctypes import Structure, c_size_t, c_uint32, c_void_p
 
 import numpy as np
@@ -54,6 +57,49 @@ class _TightenStruct(Structure):   # mirrors rc_near_tighten_t
 
 TIGHTEN_POINTERS = [name for name, _ in _TightenStruct._fields_[8:]]
 STEPS = ("rc_near_tighten_distances", "rc_near_tighten_route")
+
+# ---- beyond the table (rc_near_reach_*) ----
+MAX_EXTRA = 10               # RC_NEAR_REACH_MAX_EXTRA: 12^10 sequence numbers fit the 36 bits a best word has for them
+NO_WORD = np.uint64((1 << 64) - 1)   # a best word without a hit; else depth << 40 | level << 36 | index
+REACH_POINTERS = ("soa", "live", "best", "dist_out", "level_out", "out_queues", "out_lens", "status")
+# A work item is (state, the first min(level, P) moves); the lane of an item walks the 12^(level - P) sequences behind them.
+# P is the smallest that gives a level 2^22 items (each of the device's lanes some) and leaves an item at most REACH_WALK moves:
+# the walk keeps a key per move in registers, and three moves (1 728 sequences, about 840 of them canonical) keep four waves a SIMD.
+REACH_ITEMS_TARGET = 1 << 22
+REACH_WALK = 3
+# Sequences (12^(level - P) an item, the pruned ones counted) that one launch may cover: launch_items=None cuts a level into launches
+# of DEFAULT_LAUNCH_LEAVES // 12^(level - P) items.  profiles/near_reach_probe.txt, 1 024 states, K = 8 (2.4 GiB of table), J = 8:
+# the launches of level 8 (2 485 513 items of 12^3) take at most 0.060 s, of level 7 (29 826 161 items of 12^2) 0.046 s, a whole
+# level 6 in one launch 0.044 s; at K = 6 the longest is 0.070 s.  15-22 G probes/s, so 2^32 sequences could take 0.3 s if none were
+# pruned and every state were live: well under a second, and a level of 1 024 states at J = 8 is still about a hundred launches.
+DEFAULT_LAUNCH_LEAVES = 1 << 32
+
+
+class _ReachStruct(Structure):   # mirrors rc_near_reach_t
+    _fields_ = [("n", c_size_t), ("stride", c_size_t)] + [(name, c_uint32) for name in ("extra", "prefix", "out_width", "reserved")] + \
+               [(name, c_void_p) for name in REACH_POINTERS]
+
+
+ReachResult = namedtuple("ReachResult", "distances queues lengths levels items seconds")
+ReachResult.__doc__ = """What `NearTable.reach` returns: distances int8 [n] (-1: farther than K + extra), queues (a QueueTable of optimal
+solutions, empty where there is no distance), lengths int32 [n] (= distances), levels int8 [n] (moves walked before the table
+was hit, -1 without a distance), items (work items launched at the levels >= 1) and the wall seconds."""
+
+
+def reach_items(level: int, prefix: int) -> int:
+    """rc_near_reach_items: work items per state of a level."""
+    return 12 ** min(int(level), int(prefix))
+
+
+def default_prefix(n: int, extra: int) -> int:
+    P = 0
+    while P < extra and n * 12 ** P < REACH_ITEMS_TARGET:
+        P += 1
+    return max(P, extra - REACH_WALK)
+
+
+def default_launch_items(level: int, prefix: int) -> int:
+    return max(1, DEFAULT_LAUNCH_LEAVES // 12 ** (level - min(level, prefix)))
 
 
 # ---- planning (pure) ---------------------------------------------------------------------------------------------------------
@@ -150,6 +196,61 @@ class TightenBatch:
             self.step(name)
             b.record()
             timings.setdefault(name, []).append((a, b))
+
+
+# ---- one batch of states searched beyond the table -----------------------------------------------------------------------------
+class ReachBatch:
+    """The device arrays of one `reach` and the rc_near_reach_t that names them; `begin`, `level` and `finish` are the three entry
+    points (tests drive them by hand and read `words()` and `live` in between)."""
+
+    def __init__(self, table: "NearTable", states, extra: int, prefix: int = None, out_width: int = None):
+        self.table, self.lib = table, _hip.lib()
+        if ctypes.sizeof(_ReachStruct) != self.lib.rc_near_reach_struct_bytes():
+            raise _hip.RubiksHipError(f"rc_near_reach_t has {self.lib.rc_near_reach_struct_bytes()} bytes, its mirror {ctypes.sizeof(_ReachStruct)}")
+        extra = int(extra)
+        if not 0 <= extra <= MAX_EXTRA:
+            raise ValueError(f"extra {extra}: 0 .. {MAX_EXTRA}")
+        if prefix is not None and not 0 <= int(prefix) <= MAX_EXTRA:
+            raise ValueError(f"prefix {prefix}: 0 .. {MAX_EXTRA}")
+        self.cubes = DeviceCubes.of(states)
+        n, dev = self.cubes.n, table.device
+        assert n >= 1
+        self.n, self.extra = n, extra
+        self.prefix = default_prefix(n, extra) if prefix is None else int(prefix)
+        W = max(1, table.depth + extra if out_width is None else int(out_width))
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+        self.soa = self.cubes.soa
+        self.live, self.best = z((n,), torch.uint8), z((n,), torch.int64)    # (the words are unsigned: `words`)
+        self.dist_out, self.level_out = z((n,), torch.int8), z((n,), torch.int8)
+        self.out_queues, self.out_lens, self.status = z((n, W), torch.uint8), z((n,), torch.int32), z((2,), torch.int32)
+        s = _ReachStruct()
+        s.n, s.stride, s.extra, s.prefix, s.out_width = n, self.cubes.stride, extra, self.prefix, W
+        for name in REACH_POINTERS:
+            setattr(s, name, getattr(self, name).data_ptr())
+        self.struct = s
+
+    def _args(self):
+        return ctypes.byref(self.table.struct), ctypes.byref(self.struct)
+
+    def begin(self):
+        _hip.check(self.lib.rc_near_reach_begin(*self._args(), _hip.stream_ptr()), "rc_near_reach_begin")
+
+    def level(self, level: int, first: int, count: int):
+        _hip.check(self.lib.rc_near_reach_level(*self._args(), level, first, count, _hip.stream_ptr()), "rc_near_reach_level")
+
+    def finish(self):
+        _hip.check(self.lib.rc_near_reach_finish(*self._args(), _hip.stream_ptr()), "rc_near_reach_finish")
+
+    def items(self, level: int) -> int:
+        """Work items of the whole batch at `level`."""
+        return self.n * reach_items(level, self.prefix)
+
+    def unresolved(self) -> int:
+        """The one read between two levels: states without a distance after the calls so far."""
+        return int(self.status[1].item())
+
+    def words(self) -> np.ndarray:
+        return self.best.cpu().numpy().view(np.uint64)
 
 
 # ---- the table -----------------------------------------------------------------------------------------------------------------
@@ -262,6 +363,57 @@ class NearTable:
             self._check(status, "rc_near_solve")
         lengths = lens[:n].cpu().numpy()
         return QueueTable(rows[:n].cpu().numpy(), np.maximum(lengths, 0)), lengths
+
+    def reach(self, states, extra: int = 0, launch_items: int = None, timings: dict = None, prefix: int = None) -> ReachResult:
+        """
+        Exact distances and optimal solutions up to depth + `extra` quarter turns: the table is one half of a bidirectional search,
+        and this walks the other half.  For j = 0 .. extra in turn every sequence of j moves is applied to a state and the result
+        probed in the table; the first level with a hit gives the distance j + (smallest depth hit), and the hit with the smallest
+        (depth, sequence number) followed by its state's `solve` is the solution (the rule, and why walking only canonical
+        sequences changes nothing: include/rubiks_hip.h).  A level runs only while a state is without a distance.
+        states: (n, 20) int8 or DeviceCubes.  extra=0 is exactly `depths` and `solve`.  launch_items: work items per launch at
+        most (None: DEFAULT_LAUNCH_LEAVES sequences a launch); prefix: the moves a work item's number holds (None: chosen from n
+        and extra).  The result depends on neither.  timings: a dict that receives, per level, the HIP event pairs of its launches.
+        """
+        import time
+        extra = int(extra)
+        if not 0 <= extra <= MAX_EXTRA:
+            raise ValueError(f"extra {extra}: 0 .. {MAX_EXTRA} (a sequence's number has 36 bits)")
+        if launch_items is not None and int(launch_items) < 1:
+            raise ValueError(f"launch_items {launch_items}: at least 1 (None: {DEFAULT_LAUNCH_LEAVES} sequences a launch)")
+        if prefix is not None and not 0 <= int(prefix) <= MAX_EXTRA:
+            raise ValueError(f"prefix {prefix}: 0 .. {MAX_EXTRA}")
+        cubes = DeviceCubes.of(states)
+        n = cubes.n
+        if n == 0:
+            return ReachResult(np.zeros(0, dtype=np.int8), QueueTable(n=0), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int8), 0, 0.0)
+        t0 = time.perf_counter()
+        with torch.cuda.device(self.device):
+            batch = ReachBatch(self, cubes, extra, prefix)
+            batch.begin()
+            items = 0
+            for level in range(1, extra + 1):
+                if batch.unresolved() == 0:
+                    break
+                total = batch.items(level)
+                per = default_launch_items(level, batch.prefix) if launch_items is None else int(launch_items)
+                for first in range(0, total, per):
+                    count = min(per, total - first)
+                    if timings is not None:
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                    batch.level(level, first, count)
+                    if timings is not None:
+                        b.record()
+                        timings.setdefault(level, []).append((a, b))
+                    items += count
+            batch.finish()
+            status = int(batch.status[0].item())
+            if status != 0:
+                raise _hip.RubiksHipError("rc_near_reach: the near table's cells or meta bytes are not what the build wrote (RC_NEAR_CORRUPT)")
+            dist, levels, lengths = batch.dist_out.cpu().numpy(), batch.level_out.cpu().numpy(), batch.out_lens.cpu().numpy()
+            queues = QueueTable(batch.out_queues.cpu().numpy(), np.maximum(lengths, 0))
+        return ReachResult(dist, queues, lengths, levels, items, time.perf_counter() - t0)
 
     def tighten(self, queues, lengths=None, select=None, window=None, budget_bytes: int = None, timings: dict = None, info: dict = None):
         """

@@ -138,6 +138,23 @@ class BatchResult:
         out.shorten_seconds, out.tighten_seconds = self.shorten_seconds, time.perf_counter() - t0
         return out
 
+    def excess(self, table, states, extra: int = 0, launch_items: int = None) -> np.ndarray:
+        """
+        int32 [B]: for every SOLVED game its solution's length minus the exact distance of its scramble, found by
+        `table.reach(states, extra)` (a NearTable, librubiks/solving/near.py) -- 0 is an optimal solution; -1 where the game is
+        unsolved or the scramble lies farther than the table's depth + `extra`.  `states`: the scrambles the search was given
+        ((n, 20) int8 or DeviceCubes).  Only the solved games are searched.  Composes with the other two:
+        `result.shortened(states).tightened(table).excess(table, states, extra=4)`.
+        """
+        from librubiks.cube.device import DeviceCubes
+        solved = np.flatnonzero(np.asarray(self.solved, dtype=bool))
+        out = np.full(len(self.solved), -1, dtype=np.int32)
+        if len(solved):
+            rows = states.numpy() if isinstance(states, DeviceCubes) else np.asarray(states)
+            dist = table.reach(rows[solved], extra=extra, launch_items=launch_items).distances.astype(np.int32)
+            out[solved] = np.where(dist >= 0, np.asarray(self.lengths)[solved].astype(np.int32) - dist, -1)
+        return out
+
     @property
     def states_per_sec(self) -> float:
         return float(self.nodes.sum()) / max(self.seconds, 1e-12)
